@@ -2,7 +2,7 @@
 
 PY ?= python
 
-.PHONY: build test test-gpu bench serve doctor clean
+.PHONY: build test test-gpu bench bench-full serve doctor clean
 
 build:          ## compile the gfx950 HIP extension in-tree
 	PYTORCH_ROCM_ARCH=gfx950 $(PY) setup.py build_ext --inplace
@@ -18,6 +18,9 @@ test-gpu:       ## kernel numerics + engine + mesh integration on an MI355X
 
 bench:          ## flagship decode benchmark (one JSON line)
 	$(PY) bench.py --gpus 1 --steps 32 --warmup 8
+
+bench-full:     ## same, prefilling every prompt and tuning the GEMMs first
+	$(PY) bench.py --gpus 1 --steps 32 --warmup 8 --full
 
 preflight:      ## scale-run preflight (RCCL self-test, env, rank wiring)
 	$(PY) bench.py --preflight --gpus 8

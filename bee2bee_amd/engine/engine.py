@@ -1142,11 +1142,17 @@ class InferenceEngine:
 
     @torch.no_grad()
     def bench_prefill(self, batch: int, prompt_len: int, seed: int = 1234,
-                      max_new: Optional[int] = None) -> List[int]:
+                      max_new: Optional[int] = None,
+                      distinct: Optional[int] = None) -> List[int]:
         """Fill the KV cache with synthetic prompts; returns seq_ids.
         max_new must leave room for the prompt under max_seq_len or the
         admission truncation rule will cut the prompts short (a 10**9
-        sentinel used to truncate every bench prompt to one token)."""
+        sentinel used to truncate every bench prompt to one token).
+
+        distinct=D < batch prefills only the first D prompts; sequence j >= D
+        reuses prompt j % D and gets a COPY of its KV in blocks of its own,
+        so a decode step still reads batch * prompt_len tokens of KV from
+        distinct addresses while set-up costs D prompts of prefill."""
         if max_new is None:
             max_new = max(1, self.max_seq_len - prompt_len - 1)
         assert prompt_len + max_new < self.max_seq_len + 1, "prompt would truncate"
@@ -1160,14 +1166,28 @@ class InferenceEngine:
         ids = torch.randint(
             4, self.spec.vocab_size, (batch, prompt_len), generator=gen
         )
+        n_src = batch if distinct is None else max(1, min(distinct, batch))
         acts = []
         for b, seq_id in enumerate(seq_ids):
             req = GenerationRequest(
-                prompt_ids=ids[b].tolist(), max_new_tokens=max_new,
+                prompt_ids=ids[b % n_src].tolist(), max_new_tokens=max_new,
                 sampling=SamplingParams(greedy=True),
             )
             acts.append(_Active(req, seq_id, 0))
-        self._prefill_no_admit(acts)
+        self._prefill_no_admit(acts[:n_src])
+        # replicas: the state prefill left in their source, KV in own blocks
+        for j in range(n_src, batch):
+            a, src = acts[j], acts[j % n_src]
+            self.kv.extend_seq(a.seq_id, src.length)
+            a.prefilled = a.length = src.length
+            a.req.output_ids.append(src.req.output_ids[-1])
+        for lo in range(n_src, batch, n_src):
+            grp = acts[lo:lo + n_src]
+            dst = self.kv.block_table([a.seq_id for a in grp]).flatten().long()
+            src_blk = self.kv.block_table(
+                [a.seq_id for a in acts[:len(grp)]]).flatten().long()
+            for cache in self.kv.k_cache + self.kv.v_cache:
+                cache[dst] = cache[src_blk]
         self._bench_acts = acts
         for a in acts:
             assert a.prefilled == prompt_len, "bench prompt truncated"
@@ -1191,12 +1211,13 @@ class InferenceEngine:
 
     @torch.no_grad()
     def bench_setup(self, batch: int, prompt_len: int, steps_budget: int,
-                    seed: int = 1234) -> None:
+                    seed: int = 1234, distinct: Optional[int] = None) -> None:
         """Prefill a synthetic batch and preallocate KV for the whole run so
         the timed loop is pure device work (graph replay + sampling + buffer
-        bumps; zero host round-trips per step)."""
+        bumps; zero host round-trips per step). distinct: see bench_prefill."""
         assert batch <= self.max_batch
-        seq_ids = self.bench_prefill(batch, prompt_len, seed=seed)
+        seq_ids = self.bench_prefill(batch, prompt_len, seed=seed,
+                                     distinct=distinct)
         for sid in seq_ids:
             self.kv.extend_seq(sid, prompt_len + steps_budget + 1)
         dev = self.device

@@ -142,8 +142,8 @@ def _check_tunableop(tune_dir: str) -> Dict:
     base = os.path.join(tune_dir, "tunableop_0.csv")
     if not os.path.exists(base):
         return {"status": WARN,
-                "detail": "no rank-0 TunableOp table yet (first bench run "
-                          "tunes; later runs replay)"}
+                "detail": "no rank-0 TunableOp table yet (the first bench "
+                          "--full run tunes; later --full runs replay)"}
     missing = [d for d in range(1, 8)
                if not os.path.exists(os.path.join(tune_dir, f"tunableop_{d}.csv"))]
     if missing:

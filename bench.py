@@ -12,6 +12,15 @@ A step = one decode iteration of a fixed per-GPU batch (default 1536 seqs at
 prompt length 1024): full layer stack on the HIP kernels via hipGraph
 replay + greedy sampling + paged-KV append. Weights are random-init of the
 real architecture; prompts synthetic (no network for checkpoints).
+
+A plain run does only what the headline needs: set up, warm up, time the K
+steps, print the line. Its set-up prefills `--distinct-prompts` prompts
+(default 256) and copies their KV into blocks of their own for the rest of
+the batch: prefilling all 1536 takes ~22 s and the decode step does not
+care. `--full` prefills every prompt and adds the hipBLASLt tuning sweep
+before the timed steps. `--dump-outputs DIR` writes the last timed step's outputs as
+.npy; weights, prompts and (without --full) GEMM dispatch are fixed by the
+arguments, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -24,6 +33,42 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import torch
+
+# --dump-outputs keeps the logits file under this size by storing a fixed,
+# seeded sample of vocabulary columns (all batch rows) when the full
+# [batch, vocab] float32 array would be larger.
+DUMP_LOGITS_MAX_BYTES = 48 << 20
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(engine, out_dir: str, suffix: str = "") -> None:
+    """Write what the last bench_step() left for its caller as float32
+    .npy files: `next_ids` [batch] (the greedy tokens fed to the following
+    step) and, on the captured-graph path, `logits` [batch, n_cols] (the
+    static logits buffer of the last replay; n_cols == vocab when it fits,
+    else sorted columns drawn once with DUMP_SAMPLE_SEED). The eager path
+    does not keep its logits, so it writes `next_ids` only."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    mode, B = engine._bench_state
+    if mode == "graph":
+        g = engine.graphs
+        next_ids = g.input_ids[:B]
+        logits = g.logits[g.bucket_for(B)][:B]
+        V = logits.shape[1]
+        n_cols = min(V, DUMP_LOGITS_MAX_BYTES // (4 * B))
+        if n_cols < V:
+            cols = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(
+                V, size=n_cols, replace=False))
+            logits = logits[:, torch.from_numpy(cols).to(logits.device)]
+        np.save(os.path.join(out_dir, f"logits{suffix}.npy"),
+                logits.float().cpu().numpy())
+    else:
+        next_ids = engine._bench_eager["ids"]
+    # token ids are < 2**24: exact in float32
+    np.save(os.path.join(out_dir, f"next_ids{suffix}.npy"),
+            next_ids.to(torch.float32).cpu().numpy())
 
 
 def main() -> None:
@@ -39,7 +84,21 @@ def main() -> None:
     ap.add_argument("--prompt-len", type=int, default=1024)
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--no-tunableop", action="store_true",
-                    help="skip hipBLASLt algorithm tuning")
+                    help="skip hipBLASLt algorithm tuning (only runs with --full)")
+    ap.add_argument("--distinct-prompts", type=int, default=256,
+                    help="prefill this many distinct prompts and give the "
+                         "rest of the batch copies of their KV in blocks of "
+                         "their own (a decode step reads the same bytes; "
+                         "set-up is ~batch/N times shorter)")
+    ap.add_argument("--full", action="store_true",
+                    help="also do the work a plain run leaves out: prefill "
+                         "every prompt of the batch, and run the hipBLASLt "
+                         "algorithm tuning sweep during set-up and warmup "
+                         "(tens of seconds; tuned choices can differ from "
+                         "run to run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step computed as DIR/<name>.npy (float32)")
     ap.add_argument("--preflight", action="store_true",
                     help="run the scale-run preflight checks (RCCL self-"
                          "test, master endpoint, env, rank wiring) and exit")
@@ -57,10 +116,13 @@ def main() -> None:
     from bee2bee_amd.models.spec import resolve_spec
 
     _spec_probe = resolve_spec(args.model)
-    # Tune hipBLASLt GEMM algorithm selection during (untimed) setup/warmup:
-    # worth ~4% on the skinny decode projections. Off on CPU and for MoE
-    # (tuning the batched expert GEMM shapes takes minutes).
-    if not args.no_tunableop and torch.cuda.is_available() and not _spec_probe.is_moe:
+    # --full: tune hipBLASLt GEMM algorithm selection during (untimed)
+    # setup/warmup. A plain run keeps the library's default dispatch: the
+    # sweep takes longer than the rest of the run, and its picks are not
+    # reproducible, which --dump-outputs comparisons need. Off on CPU and
+    # for MoE (tuning the batched expert GEMM shapes takes minutes).
+    if (args.full and not args.no_tunableop and torch.cuda.is_available()
+            and not _spec_probe.is_moe):
         tune_dir = os.path.join(
             os.path.dirname(os.path.abspath(__file__)), "gpurun_out"
         )
@@ -134,7 +196,9 @@ def main() -> None:
     )
     spec = engine.spec
 
-    engine.bench_setup(args.batch, args.prompt_len, budget)
+    distinct = args.batch if args.full else max(
+        1, min(args.distinct_prompts, args.batch))
+    engine.bench_setup(args.batch, args.prompt_len, budget, distinct=distinct)
 
     def sync() -> None:
         if on_gpu:
@@ -161,6 +225,11 @@ def main() -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs:
+        # one set per rank (replica peers differ in their weights' seed)
+        dump_outputs(engine, args.dump_outputs,
+                     suffix=f"_rank{rank}" if world_size > 1 else "")
+
     ms_per_step = elapsed / args.steps * 1000.0
     total_tps = args.batch * args.steps * n_gpus / elapsed
 
@@ -185,6 +254,7 @@ def main() -> None:
                 "seq_len": args.prompt_len,
                 "parallelism": f"replica-dp{n_gpus}",
                 "decode_graphs": bool(engine.graphs is not None),
+                "distinct_prompts": distinct,
             },
         }
         print(json.dumps(result), flush=True)

@@ -41,6 +41,41 @@ def test_bench_single_process_contract():
 
 
 @pytest.mark.timeout(300)
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes float32 .npy files of the last timed step, and
+    two runs with the same arguments dump identical arrays, with --full
+    too (which may tune GEMMs on a GPU, so it is not compared); --steps
+    sets the number of timed steps."""
+    import numpy as np
+
+    dumps = []
+    for name, extra in (("a", []), ("b", []), ("c", ["--full"])):
+        d = tmp_path / name
+        out = subprocess.run(
+            [sys.executable, "bench.py", "--model", "tiny", "--batch", "3",
+             "--prompt-len", "8", "--steps", "3", "--warmup", "1",
+             "--distinct-prompts", "2", "--dump-outputs", str(d), *extra],
+            cwd=REPO, capture_output=True, text=True, timeout=240,
+        )
+        assert out.returncode == 0, out.stderr[-2000:]
+        res = _last_json(out.stdout)
+        assert res["steps"] == 3 and res["ms_per_step"] > 0
+        assert res["config"]["distinct_prompts"] == (3 if extra else 2)
+        files = sorted(p.name for p in d.iterdir())
+        assert "next_ids.npy" in files
+        assert all(f.endswith(".npy") for f in files)
+        arrs = {f: np.load(d / f) for f in files}
+        for a in arrs.values():
+            assert a.dtype in (np.float32, np.float64)
+        assert arrs["next_ids.npy"].shape == (3,)
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        dumps.append(arrs)
+    assert dumps[0].keys() == dumps[1].keys() == dumps[2].keys()
+    for f in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][f], dumps[1][f])
+
+
+@pytest.mark.timeout(300)
 def test_bench_multi_process_contract():
     """The driver's N>1 launch shape: torch.distributed.run, one JSON line
     from rank 0, whole-job aggregate value, MAX-over-ranks timing."""

@@ -285,6 +285,39 @@ def test_bench_prefill_fills_every_prompt():
         eng.shutdown()
 
 
+def test_bench_prefill_distinct_replicates_kv():
+    """bench_setup(distinct=D): sequences >= D hold a copy of sequence
+    j % D's prompt KV in blocks of their own and decode the same tokens."""
+    import torch
+
+    B, D, P = 7, 3, 16
+    eng = InferenceEngine("tiny", device="cpu", max_batch=B, max_seq_len=64,
+                          seed=7, max_prefill_tokens=32)
+    try:
+        eng.bench_setup(B, P, steps_budget=4, distinct=D)
+        acts = eng._bench_acts
+        bt = eng.kv.block_table([a.seq_id for a in acts])
+        n_prompt_blocks = -(-P // eng.kv.block_size)
+        used = bt[:, :n_prompt_blocks].flatten().tolist()
+        assert len(set(used)) == len(used)  # nobody shares a block
+        for j, a in enumerate(acts):
+            src = acts[j % D]
+            assert a.prefilled == P and eng.kv.seq_len(a.seq_id) >= P
+            assert a.req.prompt_ids == src.req.prompt_ids
+            assert a.req.output_ids == src.req.output_ids
+            assert len(a.req.output_ids) == 1
+            for cache in eng.kv.k_cache + eng.kv.v_cache:
+                for i in range(n_prompt_blocks):
+                    assert torch.equal(cache[bt[j, i]], cache[bt[j % D, i]])
+        assert eng.kv.k_cache[0][bt[0, 0]].abs().sum() > 0
+        for _ in range(3):
+            eng.bench_step()
+        ids = eng._bench_eager["ids"]
+        assert torch.equal(ids, ids[torch.arange(B) % D])
+    finally:
+        eng.shutdown()
+
+
 def test_repetition_penalty_seen_mask_equals_history_rebuild():
     """The pooled seen-mask penalty (incremental) must emit exactly the
     tokens of the host-rebuilt-history fallback path."""

@@ -124,6 +124,47 @@ def test_graph_vs_eager_logits():
         eng.shutdown()
 
 
+def test_bench_dump_outputs_graph_path(tmp_path, monkeypatch):
+    """bench.py --dump-outputs on the captured-graph path: float32 files of
+    the last step's logits and greedy ids; the ids are the argmax of the
+    dumped logits, and a capped dump is the seeded column sample of the
+    full one."""
+    import numpy as np
+
+    import bench
+
+    eng = InferenceEngine(
+        "llama3.2-1b", device="cuda:0", max_batch=2, max_seq_len=256,
+        use_graphs=True, seed=11,
+    )
+    try:
+        B, P = 2, 32
+        eng.bench_setup(B, P, steps_budget=4)
+        eng.bench_step()
+        eng.bench_step()
+        bench.dump_outputs(eng, str(tmp_path / "full"))
+        V = eng.spec.vocab_size
+        n_cols = 1000
+        monkeypatch.setattr(bench, "DUMP_LOGITS_MAX_BYTES", 4 * B * n_cols)
+        bench.dump_outputs(eng, str(tmp_path / "capped"), suffix="_rank1")
+    finally:
+        eng.shutdown()
+    logits = np.load(tmp_path / "full" / "logits.npy")
+    ids = np.load(tmp_path / "full" / "next_ids.npy")
+    assert logits.dtype == np.float32 and ids.dtype == np.float32
+    assert logits.shape == (B, V) and ids.shape == (B,)
+    assert np.isfinite(logits).all()
+    # (bf16 logits can tie exactly: compare values, not argmax indices)
+    np.testing.assert_array_equal(
+        logits[np.arange(B), ids.astype(np.int64)], logits.max(axis=1))
+    capped = np.load(tmp_path / "capped" / "logits_rank1.npy")
+    cols = np.sort(np.random.default_rng(bench.DUMP_SAMPLE_SEED).choice(
+        V, size=n_cols, replace=False))
+    np.testing.assert_array_equal(capped, logits[:, cols])
+    np.testing.assert_array_equal(
+        np.load(tmp_path / "capped" / "next_ids_rank1.npy"), ids)
+
+
 def test_concurrent_requests_complete(engine):
     """Continuous batching: concurrent requests all complete with the right
     lengths and bounded drift vs solo runs (exact token equality is not
