@@ -29,6 +29,32 @@ def _serve(backend: str, **kwargs) -> None:
     asyncio.run(run_mesh_node(bootstrap_link=bootstrap, backend=backend, **kwargs))
 
 
+_KV_FP8_HELP = ("fp8 (OCP e4m3) KV cache: half the decode-attention "
+                "bytes at a small quantization cost")
+_KV_SCALES_HELP = ("per-head fp8 KV scales: a scales file PATH, 'checkpoint' "
+                   "(k_scale/v_scale tensors of the HF checkpoint) or "
+                   "'calibrate' (measure at start-up); needs --kv-fp8")
+_KV_SCALES_OUT_HELP = "with --kv-scales calibrate: save the scales to PATH"
+
+
+def _kv_env(kv_fp8: bool, kv_scales, kv_scales_out) -> None:
+    """Validate the fp8-KV flags and hand them to the native service through
+    their env twins (BEE2BEE_KV_FP8 / BEE2BEE_KV_SCALES[_OUT])."""
+    if kv_fp8:
+        os.environ["BEE2BEE_KV_FP8"] = "1"
+    if kv_scales:
+        if os.environ.get("BEE2BEE_KV_FP8") != "1":
+            raise click.UsageError(
+                "--kv-scales needs the fp8 KV cache: add --kv-fp8 "
+                "(per-head scales do nothing for a bf16 cache)")
+        os.environ["BEE2BEE_KV_SCALES"] = kv_scales
+    if kv_scales_out:
+        if kv_scales != "calibrate":
+            raise click.UsageError(
+                "--kv-scales-out only applies with --kv-scales calibrate")
+        os.environ["BEE2BEE_KV_SCALES_OUT"] = kv_scales_out
+
+
 @cli.command("serve-hf")
 @click.option("--model", default="distilgpt2", help="Model name (preset or HF id)")
 @click.option("--model-path", default=None, help="Local HF checkpoint dir (safetensors)")
@@ -36,11 +62,18 @@ def _serve(backend: str, **kwargs) -> None:
 @click.option("--region", default="Auto", help="Region name")
 @click.option("--api-port", default=8000, type=int, help="FastAPI port")
 @click.option("--device", default=None, help="cuda:N / cpu (auto when omitted)")
-def serve_hf(model, model_path, port, region, api_port, device):
+@click.option("--kv-fp8", is_flag=True, help=_KV_FP8_HELP)
+@click.option("--kv-scales", default=None, metavar="PATH|checkpoint|calibrate",
+              help=_KV_SCALES_HELP)
+@click.option("--kv-scales-out", default=None, metavar="PATH",
+              help=_KV_SCALES_OUT_HELP)
+def serve_hf(model, model_path, port, region, api_port, device, kv_fp8,
+             kv_scales, kv_scales_out):
     """Serve a model on the native MI355X engine (HF-checkpoint compatible).
 
     Named serve-hf for reference-CLI compatibility; the execution engine is
     the hand-written CDNA4 HIP runtime, not transformers."""
+    _kv_env(kv_fp8, kv_scales, kv_scales_out)
     _serve(
         "native",
         model_name=model,
@@ -62,18 +95,17 @@ def serve_hf(model, model_path, port, region, api_port, device):
 @click.option("--spec-decode", is_flag=True,
               help="speculative decoding (prompt-lookup + exact greedy "
                    "verification; output-invariant)")
-@click.option("--kv-fp8", is_flag=True,
-              help="fp8 (OCP e4m3) KV cache: half the decode-attention "
-                   "bytes at a small quantization cost")
+@click.option("--kv-fp8", is_flag=True, help=_KV_FP8_HELP)
+@click.option("--kv-scales", default=None, metavar="PATH|checkpoint|calibrate",
+              help=_KV_SCALES_HELP)
+@click.option("--kv-scales-out", default=None, metavar="PATH",
+              help=_KV_SCALES_OUT_HELP)
 def serve_native(model, model_path, port, region, api_port, device,
-                 spec_decode, kv_fp8):
+                 spec_decode, kv_fp8, kv_scales, kv_scales_out):
     """Serve a model on the native MI355X HIP engine (alias of serve-hf)."""
-    import os
-
     if spec_decode:
         os.environ["BEE2BEE_SPEC_DECODE"] = "1"
-    if kv_fp8:
-        os.environ["BEE2BEE_KV_FP8"] = "1"
+    _kv_env(kv_fp8, kv_scales, kv_scales_out)
     _serve(
         "native",
         model_name=model,

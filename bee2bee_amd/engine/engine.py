@@ -9,13 +9,14 @@ retirement, so the 288 GB HBM pool is shared across the whole request mix.
 """
 from __future__ import annotations
 
+import json
 import logging
 import os
 import queue
 import threading
 import time
 from dataclasses import dataclass, field
-from typing import Any, Dict, List, Optional
+from typing import Any, Dict, List, Optional, Sequence, Union
 
 import torch
 
@@ -32,6 +33,70 @@ from .sampler import SamplingParams, sample
 logger = logging.getLogger("bee2bee_amd.engine")
 
 _STREAM_END = object()
+
+# fp8 KV scales file: small JSON, one scale per (layer, kv head)
+KV_SCALES_FORMAT = "bee2bee-kv-scales-v1"
+# e4m3 finite maximum; calibration maps amax * margin onto it
+E4M3_MAX = 448.0
+# amax floor: an all-zero head still gets a finite positive scale
+KV_AMAX_FLOOR = 1e-6
+
+
+def load_kv_scales_file(path: str, spec: ModelSpec):
+    """Read a KV scales file and validate it against the model spec.
+    Returns (k_scale, v_scale) fp32 [n_layers, n_kv_heads]; raises
+    ValueError on any mismatch."""
+    with open(path, "r", encoding="utf-8") as f:
+        doc = json.load(f)
+    if not isinstance(doc, dict) or doc.get("format") != KV_SCALES_FORMAT:
+        raise ValueError(
+            f"{path}: not a KV scales file (format != {KV_SCALES_FORMAT!r})")
+    for key, want in (("n_layers", spec.n_layers),
+                      ("n_kv_heads", spec.n_kv_heads)):
+        if doc.get(key) != want:
+            raise ValueError(
+                f"{path}: {key}={doc.get(key)!r} does not match model "
+                f"{spec.name} ({key}={want})")
+    out = []
+    for key in ("k_scale", "v_scale"):
+        try:
+            t = torch.tensor(doc[key], dtype=torch.float32)
+        except (KeyError, TypeError, ValueError) as e:
+            raise ValueError(f"{path}: bad or missing {key}: {e}") from None
+        if tuple(t.shape) != (spec.n_layers, spec.n_kv_heads):
+            raise ValueError(
+                f"{path}: {key} has shape {tuple(t.shape)}, expected "
+                f"({spec.n_layers}, {spec.n_kv_heads})")
+        out.append(t)
+    return out[0], out[1]
+
+
+# start-up calibration set (serve --kv-scales calibrate): a few natural-
+# language/code strings through the model's tokenizer plus a few synthetic
+# uniform-random token sequences, so rare-token K/V outliers count too
+_CALIBRATION_TEXTS = (
+    "The quick brown fox jumps over the lazy dog. " * 8,
+    "Q: What is the capital of France?\nA: The capital of France is Paris. "
+    "Q: What is 12 times 12?\nA: 144.",
+    "def fib(n):\n    a, b = 0, 1\n    for _ in range(n):\n"
+    "        a, b = b, a + b\n    return a\n",
+    "In 1969, Apollo 11 landed on the Moon; 3.14159 and 2.71828 are "
+    "constants, and {\"key\": [1, 2, 3]} is JSON.",
+)
+
+
+def default_calibration_prompts(engine: "InferenceEngine",
+                                n_synthetic: int = 4,
+                                synthetic_len: int = 256) -> List[List[int]]:
+    """The built-in calibration prompts as token-id lists."""
+    prompts = [engine.tokenizer.encode(t) for t in _CALIBRATION_TEXTS]
+    gen = torch.Generator().manual_seed(20240)
+    n = min(synthetic_len, engine.max_seq_len - 1)
+    lo = min(4, engine.spec.vocab_size - 1)
+    for _ in range(n_synthetic):
+        prompts.append(torch.randint(
+            lo, engine.spec.vocab_size, (n,), generator=gen).tolist())
+    return [p for p in prompts if p]
 
 
 class TextStreamDecoder:
@@ -208,7 +273,16 @@ class InferenceEngine:
         spec_k: int = 4,
         spec_ngram: int = 2,
         kv_dtype: str = "native",
+        kv_scales: Optional[str] = None,
     ) -> None:
+        """kv_scales (fp8 KV only): None keeps unit scales; a path loads a
+        scales file written by save_kv_scales(); "checkpoint" uses the
+        self_attn.k_scale / v_scale tensors of the HF checkpoint. Run
+        calibrate_kv_scales() to measure them instead."""
+        if kv_scales is not None and kv_dtype != "fp8":
+            raise ValueError(
+                "kv_scales given but the KV cache is not fp8: per-head KV "
+                "scales only apply with kv_dtype='fp8'")
         # cap on prompt tokens prefill-batched per step: bounds time-to-first
         # -token for requests behind a burst (they decode while later
         # arrivals prefill)
@@ -265,15 +339,28 @@ class InferenceEngine:
 
         blocks_per_seq = -(-self.max_seq_len // kv_mod.BLOCK_SIZE)
         n_blocks = max_batch * blocks_per_seq + kv_margin_blocks
-        # "fp8": OCP e4m3 KV pool — half the decode-attention bytes; the
-        # chunked-prefill and speculative paths read the cache as bf16 and
-        # are not fp8-enabled yet, so they are rejected up front
+        # "fp8": OCP e4m3 KV pool — half the decode-attention bytes, with
+        # per-(layer, kv head) scales (unit until calibrated or loaded).
+        # The speculative path is not fp8-enabled yet and is rejected up
+        # front
         self.kv_dtype = kv_dtype
         if kv_dtype == "fp8" and spec_decode:
             raise ValueError("fp8 KV does not support spec_decode yet")
         self.kv = PagedKV(self.spec, self.device, dtype, n_blocks=n_blocks,
                           kv_dtype=kv_dtype)
         self.runner = Runner(self.spec, self.weights, self.kv, self.device, dtype)
+        if kv_scales == "checkpoint":
+            ck = self.weights.kv_scales
+            if ck is None:
+                raise ValueError(
+                    "kv_scales='checkpoint' but the checkpoint "
+                    f"({model_path or 'random init'}) has no "
+                    "self_attn.k_scale / v_scale tensors")
+            self.kv.set_scales(ck["k_scale"], ck["v_scale"],
+                               source="checkpoint")
+        elif kv_scales is not None:
+            ks, vs = load_kv_scales_file(kv_scales, self.spec)
+            self.kv.set_scales(ks, vs, source="file")
 
         # MoE captures while every decode bucket takes a capture-safe path:
         # dense all-experts bmm, or the grouped-GEMM kernel (device-side
@@ -339,6 +426,86 @@ class InferenceEngine:
         if self._thread is not None:
             self._thread.join(timeout=30)
             self._thread = None
+
+    # ------------------------------------------------------- fp8 KV scales
+
+    def _require_idle(self, what: str) -> None:
+        if self._active or self._prefilling or not self._pending.empty():
+            raise RuntimeError(f"{what} needs an idle engine (requests are "
+                               "active or queued)")
+
+    @torch.no_grad()
+    def calibrate_kv_scales(
+        self, prompts: Sequence[Union[str, Sequence[int]]],
+        margin: float = 2.0,
+    ) -> None:
+        """Measure per-(layer, kv head) fp8 KV scales: run the prompts
+        (token-id lists or strings) through the whole-prompt prefill with
+        an observer that keeps the running amax of post-RoPE K and of V,
+        then set scale = amax * margin / 448. margin=2.0 leaves one binade
+        of headroom, which costs e4m3 (a floating format) no relative
+        precision in its normal range — it only moves the subnormal floor.
+        Not a hot path: torch reductions, one host read at the end."""
+        if self.kv_dtype != "fp8":
+            raise ValueError("calibrate_kv_scales needs kv_dtype='fp8'")
+        if not margin > 0:
+            raise ValueError("margin must be positive")
+        self._require_idle("calibrate_kv_scales")
+        self.kv.check_scales_mutable()
+        if not prompts:
+            raise ValueError("calibrate_kv_scales needs at least one prompt")
+        s, dev = self.spec, self.device
+        amax = torch.zeros(2, s.n_layers, s.n_kv_heads, dtype=torch.float32,
+                           device=dev)
+
+        def observe(layer_idx, k, v):
+            for row, t in ((amax[0, layer_idx], k), (amax[1, layer_idx], v)):
+                torch.maximum(row, t.abs().amax(dim=(0, 2)).float(), out=row)
+
+        self.runner.kv_observer = observe
+        try:
+            for p in prompts:
+                ids = self.tokenizer.encode(p) if isinstance(p, str) else list(p)
+                ids = ids[: self.max_seq_len - 1] or [self.spec.bos_token_id]
+                seq_id = self._next_seq
+                self._next_seq += 1
+                self.kv.new_seq(seq_id)
+                try:
+                    n = len(ids)
+                    self.kv.extend_seq(seq_id, n)
+                    slots = self.kv.slot_mapping(seq_id, range(n))
+                    self.runner.forward_prefill(
+                        torch.tensor(ids, dtype=torch.int64, device=dev),
+                        torch.arange(n, dtype=torch.int32, device=dev),
+                        torch.tensor(slots, dtype=torch.int32, device=dev),
+                        torch.tensor([0, n], dtype=torch.int32, device=dev),
+                        n,
+                    )
+                finally:
+                    self.kv.free_seq(seq_id)
+        finally:
+            self.runner.kv_observer = None
+        amax = amax.cpu()  # the one host read
+        if not bool(torch.isfinite(amax).all()):
+            raise RuntimeError("calibration saw non-finite K/V values")
+        scale = amax.clamp_min(KV_AMAX_FLOOR) * (float(margin) / E4M3_MAX)
+        self.kv.set_scales(scale[0], scale[1], source="calibrated")
+
+    def save_kv_scales(self, path: str) -> None:
+        """Write the current scales as a small JSON file that
+        InferenceEngine(..., kv_scales=path) loads back bit-equal."""
+        if self.kv_dtype != "fp8":
+            raise ValueError("save_kv_scales needs kv_dtype='fp8'")
+        doc = {
+            "format": KV_SCALES_FORMAT,
+            "model": self.spec.name,
+            "n_layers": self.spec.n_layers,
+            "n_kv_heads": self.spec.n_kv_heads,
+            "k_scale": self.kv.k_scale.cpu().tolist(),
+            "v_scale": self.kv.v_scale.cpu().tolist(),
+        }
+        with open(path, "w", encoding="utf-8") as f:
+            json.dump(doc, f)
 
     # -------------------------------------------------------------- serving
 
@@ -1111,6 +1278,7 @@ class InferenceEngine:
             "model": self.spec.name,
             "device": str(self.device),
             "kv_dtype": self.kv_dtype,
+            "kv_scales": self.kv.scales_source,
             "active_requests": len(self._active),
             "prefilling_requests": len(self._prefilling),
             "queued_requests": self._pending.qsize(),

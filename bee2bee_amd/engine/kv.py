@@ -58,6 +58,74 @@ class PagedKV:
         self._free: List[int] = list(range(n_blocks - 1, -1, -1))
         self._seq_blocks: Dict[int, List[int]] = {}
         self._seq_len: Dict[int, int] = {}
+        # Per-(local layer, kv head) fp8 scales: value = float(byte) * scale,
+        # byte = e4m3(clamp(x * inv_scale, +-448)). Allocated ONCE and only
+        # ever updated in place, so a captured decode graph (which holds the
+        # row views below by address) sees new values without recapture.
+        # All ones until set_scales(): a never-calibrated fp8 cache stores
+        # and reads exactly as with the fixed unit scale.
+        self.k_scale = self.v_scale = None
+        self.k_inv_scale = self.v_inv_scale = None
+        self.scales_source = "unit"
+        self._scale_rows: List[Tuple[torch.Tensor, ...]] = []
+        if kv_dtype == "fp8":
+            ones = lambda: torch.ones(  # noqa: E731
+                hi - lo, spec.n_kv_heads, dtype=torch.float32, device=device)
+            self.k_scale, self.v_scale = ones(), ones()
+            self.k_inv_scale, self.v_inv_scale = ones(), ones()
+            self._scale_rows = [
+                (self.k_scale[i], self.v_scale[i],
+                 self.k_inv_scale[i], self.v_inv_scale[i])
+                for i in range(hi - lo)
+            ]
+
+    # scratch sequence id (pad rows of graph-bucket batches, engine.py): the
+    # one sequence allowed to hold blocks while scales change
+    SCRATCH_SEQ = -1
+
+    def layer_scales(self, layer_idx: int):
+        """(k_scale, v_scale, k_inv_scale, v_inv_scale) fp32 [n_kv_heads]
+        row views for a layer, or None for a non-fp8 cache."""
+        if not self._scale_rows:
+            return None
+        return self._scale_rows[layer_idx - self.layer_lo]
+
+    def check_scales_mutable(self) -> None:
+        """Raise unless the scales may change now: an fp8 cache in which no
+        sequence but the scratch one holds blocks."""
+        if self.kv_dtype != "fp8":
+            raise ValueError("KV scales need kv_dtype='fp8'")
+        live = [s for s, b in self._seq_blocks.items()
+                if b and s != self.SCRATCH_SEQ]
+        if live:
+            raise RuntimeError(
+                f"cannot change KV scales while sequences {live[:4]} hold "
+                "cache blocks")
+
+    def set_scales(self, k_scale: torch.Tensor, v_scale: torch.Tensor,
+                   source: str = "calibrated") -> None:
+        """Install per-(layer, kv head) scales ([n_layers_local, n_kv_heads],
+        finite and > 0) in place. Refused while any sequence but the scratch
+        one holds blocks: bytes already stored would be read back with the
+        wrong scale."""
+        self.check_scales_mutable()
+        shape = tuple(self.k_scale.shape)
+        new = []
+        for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+            t = torch.as_tensor(t, dtype=torch.float32)
+            if tuple(t.shape) != shape:
+                raise ValueError(
+                    f"{name} has shape {tuple(t.shape)}, expected {shape} "
+                    "([n_layers_local, n_kv_heads])")
+            if not bool((torch.isfinite(t) & (t > 0)).all()):
+                raise ValueError(f"{name} must be finite and positive")
+            new.append(t.to(self.device))
+        self.k_scale.copy_(new[0])
+        self.v_scale.copy_(new[1])
+        # reciprocals once, with torch: no device-side division in kernels
+        self.k_inv_scale.copy_(1.0 / self.k_scale)
+        self.v_inv_scale.copy_(1.0 / self.v_scale)
+        self.scales_source = source
 
     def layer(self, layer_idx: int) -> Tuple[torch.Tensor, torch.Tensor]:
         return self.k_cache[layer_idx - self.layer_lo], self.v_cache[layer_idx - self.layer_lo]

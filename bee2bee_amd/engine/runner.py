@@ -47,6 +47,9 @@ class Runner:
         # all-reduce their partial outputs over RCCL
         self.tp_group = None
         self.decode_attn_fn = None  # CP hook (parallel/cp.py)
+        # calibration hook (engine.calibrate_kv_scales): called per layer as
+        # kv_observer(layer_idx, k, v) with post-RoPE K and V [T, nkv, hd]
+        self.kv_observer = None
         cos, sin = ops.rope_tables(
             spec.max_seq_len, spec.head_dim, spec.rope_theta, device,
             scaling=spec.rope_scaling,
@@ -114,8 +117,15 @@ class Runner:
         v = v.view(T, s.n_kv_heads, s.head_dim)
         if s.pos_type == "rope":
             ops.rope_inplace(q, k, positions, self.rope_cos, self.rope_sin)
+        if self.kv_observer is not None:
+            self.kv_observer(layer_idx, k, v)
         k_cache, v_cache = self.kv.layer(layer_idx)
-        ops.kv_cache_store(k, v, k_cache, v_cache, slot_mapping)
+        sc = self.kv.layer_scales(layer_idx)
+        if sc is None:
+            ops.kv_cache_store(k, v, k_cache, v_cache, slot_mapping)
+        else:  # fp8 cache: per-kv-head scales (all ones until calibrated)
+            ops.kv_cache_store(k, v, k_cache, v_cache, slot_mapping,
+                               k_inv_scale=sc[2], v_inv_scale=sc[3])
         attn_out = attn_fn(layer_idx, q, k, v, k_cache, v_cache)
         attn_out = F.linear(attn_out.reshape(T, s.q_size), lw.wo, lw.wo_bias)
         if self.tp_group is not None:
@@ -315,9 +325,12 @@ class Runner:
                 # kernel reads K/V exclusively from the paged cache and masks
                 # causally at absolute positions (HIP attn_prefill_mfma
                 # <HD, PAGED=true>; reference attn_decode_with_history on CPU)
+                sc = self.kv.layer_scales(layer_idx)
+                kw = {} if sc is None else {"k_scale": sc[0],
+                                            "v_scale": sc[1]}
                 return ops.attn_prefill_paged(
                     q, k_cache, v_cache, block_table, seq_lens, cu_seqlens,
-                    max_seqlen, self.scale,
+                    max_seqlen, self.scale, **kw
                 )
             return ops.attn_prefill(q, k, v, cu_seqlens, max_seqlen, self.scale)
 
@@ -340,14 +353,17 @@ class Runner:
         later pipeline stages); returns final hidden [B, H]."""
 
         def attn(layer_idx, q, k, v, k_cache, v_cache):
+            sc = self.kv.layer_scales(layer_idx)
+            kw = {} if sc is None else {"k_scale": sc[0], "v_scale": sc[1]}
             if self.decode_attn_fn is not None:
                 # injected attention (context parallelism: parallel/cp.py
                 # merges per-rank partials over the local KV shard)
                 return self.decode_attn_fn(
-                    q, k_cache, v_cache, block_table, seq_lens, self.scale
+                    q, k_cache, v_cache, block_table, seq_lens, self.scale,
+                    **kw
                 )
             return ops.attn_decode(
-                q, k_cache, v_cache, block_table, seq_lens, self.scale
+                q, k_cache, v_cache, block_table, seq_lens, self.scale, **kw
             )
 
         hidden = (

@@ -69,6 +69,11 @@ class ModelWeights:
         # expert-parallel shard: when set, MoE expert tensors hold only
         # experts [lo, hi) (gate stays replicated); see parallel/ep.py
         self.expert_range: Optional[Tuple[int, int]] = None
+        # fp8-KV checkpoints ship per-layer self_attn.k_scale / v_scale:
+        # {"k_scale": [n_layers, n_kv_heads] fp32 (cpu), "v_scale": same},
+        # or None when the checkpoint has none (InferenceEngine
+        # kv_scales="checkpoint" consumes them)
+        self.kv_scales: Optional[Dict[str, torch.Tensor]] = None
 
     # -------------------------------------------------------------- random
 
@@ -190,9 +195,21 @@ class ModelWeights:
         want_head = hi == s.n_layers
 
         pending: Dict[str, Dict[str, torch.Tensor]] = {}
+        kv_scales: Dict[str, Dict[int, torch.Tensor]] = {
+            "k_scale": {}, "v_scale": {}}
 
         def to_dev(t: torch.Tensor) -> torch.Tensor:
             return t.to(self.device, self.dtype, non_blocking=True)
+
+        def head_scale(name: str, t: torch.Tensor) -> torch.Tensor:
+            t = t.detach().to("cpu", torch.float32).reshape(-1)
+            if t.numel() == 1:  # per-tensor scale: broadcast across heads
+                t = t.expand(s.n_kv_heads)
+            if t.numel() != s.n_kv_heads:
+                raise ValueError(
+                    f"{name}: expected a scalar or [{s.n_kv_heads}] "
+                    f"per-kv-head scale, got {t.numel()} values")
+            return t.clone()
 
         def try_fuse(i: int) -> None:
             lw = self.layers[i]
@@ -258,6 +275,8 @@ class ModelWeights:
                 try_fuse(i)
             elif sub == "self_attn.o_proj.weight":
                 lw.wo = to_dev(tensor)
+            elif sub in ("self_attn.k_scale", "self_attn.v_scale"):
+                kv_scales[parts[4]][i] = head_scale(name, tensor)
             elif sub == "mlp.gate_proj.weight":
                 pending.setdefault(f"mlp.{i}", {})["gate"] = to_dev(tensor)
                 try_fuse(i)
@@ -301,6 +320,20 @@ class ModelWeights:
             raise FileNotFoundError(
                 f"checkpoint at {model_path} is missing tensors: {missing[:5]}"
             )
+        if kv_scales["k_scale"] or kv_scales["v_scale"]:
+            # layers outside [lo, hi) (other pipeline stages) stay at 1.0
+            out = {}
+            for key, rows in kv_scales.items():
+                absent = [i for i in range(lo, hi) if i not in rows]
+                if absent:
+                    raise ValueError(
+                        f"checkpoint at {model_path} has self_attn.{key} for "
+                        f"some layers but not layers {absent[:5]}")
+                t = torch.ones(s.n_layers, s.n_kv_heads, dtype=torch.float32)
+                for i, row in rows.items():
+                    t[i] = row
+                out[key] = t
+            self.kv_scales = out
         return self
 
 

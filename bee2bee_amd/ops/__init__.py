@@ -117,11 +117,18 @@ def kv_cache_store(
     k_cache: torch.Tensor,
     v_cache: torch.Tensor,
     slot_mapping: torch.Tensor,
+    k_inv_scale: Optional[torch.Tensor] = None,
+    v_inv_scale: Optional[torch.Tensor] = None,
 ) -> None:
+    """k_inv_scale / v_inv_scale: optional fp32 [n_kv_heads] reciprocal
+    scales of a scaled fp8 cache (byte = e4m3(clamp(x * inv_scale[h],
+    +-448))). None stores with the fixed unit scale."""
     if _use_hip(k):
-        require_hip().kv_cache_store(k, v, k_cache, v_cache, slot_mapping)
+        require_hip().kv_cache_store(k, v, k_cache, v_cache, slot_mapping,
+                                     k_inv_scale, v_inv_scale)
         return
-    reference.kv_cache_store(k, v, k_cache, v_cache, slot_mapping)
+    reference.kv_cache_store(k, v, k_cache, v_cache, slot_mapping,
+                             k_inv_scale, v_inv_scale)
 
 
 def attn_decode(
@@ -131,12 +138,17 @@ def attn_decode(
     block_table: torch.Tensor,
     seq_lens: torch.Tensor,
     scale: float,
+    k_scale: Optional[torch.Tensor] = None,
+    v_scale: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
+    """k_scale / v_scale: optional fp32 [n_kv_heads] dequantization scales
+    of a scaled fp8 cache (value = float(byte) * scale[h])."""
     if _use_hip(q):
         return require_hip().attn_decode(
-            q, k_cache, v_cache, block_table, seq_lens, scale
+            q, k_cache, v_cache, block_table, seq_lens, scale, k_scale, v_scale
         )
-    return reference.attn_decode(q, k_cache, v_cache, block_table, seq_lens, scale)
+    return reference.attn_decode(q, k_cache, v_cache, block_table, seq_lens,
+                                 scale, k_scale=k_scale, v_scale=v_scale)
 
 
 def attn_decode_lse(
@@ -146,16 +158,19 @@ def attn_decode_lse(
     block_table: torch.Tensor,
     seq_lens: torch.Tensor,
     scale: float,
+    k_scale: Optional[torch.Tensor] = None,
+    v_scale: Optional[torch.Tensor] = None,
 ):
     """attn_decode that ALSO returns the per-(seq, q-head) flash merge
     state (m, l) — what context-parallel ranks exchange (parallel/cp.py)."""
     if _use_hip(q):
         out, ml = require_hip().attn_decode_lse(
-            q, k_cache, v_cache, block_table, seq_lens, scale
+            q, k_cache, v_cache, block_table, seq_lens, scale, k_scale, v_scale
         )
         return out, ml
     return reference.attn_decode_lse(
-        q, k_cache, v_cache, block_table, seq_lens, scale)
+        q, k_cache, v_cache, block_table, seq_lens, scale,
+        k_scale=k_scale, v_scale=v_scale)
 
 
 def attn_prefill(
@@ -183,16 +198,20 @@ def attn_prefill_paged(
     cu_q: torch.Tensor,
     max_qlen: int,
     scale: float,
+    k_scale: Optional[torch.Tensor] = None,
+    v_scale: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Chunked prefill: packed query chunks (cu_q) attend to the full paged
     history (seq_lens includes the chunk; its K/V are already stored)."""
     if _use_hip(q):
         return require_hip().attn_prefill_paged(
-            q, k_cache, v_cache, block_table, seq_lens, cu_q, max_qlen, scale
+            q, k_cache, v_cache, block_table, seq_lens, cu_q, max_qlen, scale,
+            k_scale, v_scale
         )
     query_lens = cu_q[1:] - cu_q[:-1]
     return reference.attn_decode_with_history(
-        q, k_cache, v_cache, block_table, seq_lens, query_lens, scale
+        q, k_cache, v_cache, block_table, seq_lens, query_lens, scale,
+        k_scale=k_scale, v_scale=v_scale
     )
 
 

@@ -13,6 +13,24 @@
 //   3. attn_combine: merge chunk partials, normalize, write bf16 out
 // Scratch p traffic is ~3% of KV traffic.
 //
+// Per-kv-head fp8 scales (scaled fp8 cache, value = float(byte)*scale[h]):
+// k_scale multiplies the fp32 SCORE after the dot product / MFMA (never the
+// staged q: on the fp8 path q is itself quantized to e4m3, and a typical
+// k_scale ~0.05 would push it into subnormals), so the chunk (m, l) come
+// from scaled scores and combine / FOLD / out_ml need no change. (The
+// scaled MFMA kernel also lifts a staged q that would underflow e4m3 by a
+// power of two and divides it back out of the score — see the kernel.)
+// v_scale multiplies the PV accumulator once: where part_o is written
+// (non-FOLD) or at the final out write (FOLD). kvh is blockIdx.y, so both
+// scales are scalar loads held in an SGPR. The unscaled path: the MFMA scores kernel
+// takes a SCALED template flag (a runtime null-pointer branch around the
+// multiply made the allocator move the MFMA results through more AGPRs and
+// cost the unscaled fp8 instantiations a wave of occupancy; with the flag
+// the unscaled code is the same as before); the generic scores kernel and
+// the PV kernel use a uniform null-pointer branch, which left their
+// register counts unchanged. The bf16 instantiations compile the scale
+// code away.
+//
 // Replaces: the reference's decode path inside transformers.generate()
 // (bee2bee/hf.py:84-108). Numerics reference: ops/reference.py attn_decode.
 #include "common.h"
@@ -149,13 +167,16 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_scores_kernel(
     const int* __restrict__ seq_lens,            // [B]
     unsigned short* __restrict__ p_out,          // [B, nkv, C, CHUNK, G] bf16
     float* __restrict__ part_ml,                 // [B, nkv, C, G, 2]
-    int nkv, int W, int bs, int hd, int C, long q_stride, float scale) {
+    int nkv, int W, int bs, int hd, int C, long q_stride, float scale,
+    const float* __restrict__ k_scale) {         // [nkv] or nullptr
     const int b = blockIdx.x;
     const int kvh = blockIdx.y;
     const int L = seq_lens[b];
     if ((int)blockIdx.z * DEC_CHUNK >= L) return;
     const int lane = threadIdx.x % WAVE;
     const int wid = threadIdx.x / WAVE;
+    const bool scaled = sizeof(KVT) == 1 && k_scale != nullptr;
+    const float ksc = scaled ? k_scale[kvh] : 1.f;
 
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     unsigned short* q_s = reinterpret_cast<unsigned short*>(smem_raw);  // [G*hd]
@@ -206,6 +227,10 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_scores_kernel(
                                     bf2f((unsigned short)qraw[j]), s[g]);
                 }
             }
+        }
+        if (scaled) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) s[g] *= ksc;
         }
     }
 
@@ -273,7 +298,7 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_scores_kernel(
 //   A (16x32): lane = row (l&15), k = (l>>4)*8+e
 //   B (32x16): lane = col (l&15), k = (l>>4)*8+e
 //   C (16x16): lane = col (l&15), row = (l>>4)*4+r
-template <int G, int HD, typename KVT>
+template <int G, int HD, typename KVT, bool SCALED>
 __global__ __launch_bounds__(DEC_BLOCK) void attn_scores_mfma_kernel(
     const unsigned short* __restrict__ q,
     const KVT* __restrict__ k_cache,
@@ -281,13 +306,16 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_scores_mfma_kernel(
     const int* __restrict__ seq_lens,
     unsigned short* __restrict__ p_out,  // bf16
     float* __restrict__ part_ml,
-    int nkv, int W, int bs, int C, long q_stride, float scale) {
+    int nkv, int W, int bs, int C, long q_stride, float scale,
+    const float* __restrict__ k_scale) {  // [nkv]; read iff SCALED
     constexpr int KSTEPS = HD / 32;
     constexpr int TILES = WAVE / 16;  // 4 key-tiles of 16 per wave
     const int b = blockIdx.x;
     const int kvh = blockIdx.y;
     const int L = seq_lens[b];
     if ((int)blockIdx.z * DEC_CHUNK >= L) return;
+    float ksc = 1.f;
+    if (SCALED) ksc = k_scale[kvh];  // uniform: one scalar load
     const int lane = threadIdx.x % WAVE;
     const int wid = threadIdx.x / WAVE;
     const int lg = lane >> 4;  // lane group 0..3
@@ -298,10 +326,47 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_scores_mfma_kernel(
     float* red = reinterpret_cast<float*>(smem_raw + ((G * HD * 2 + 15) & ~15));
     // red: [DEC_WAVES][G][2]
 
-    for (int i = threadIdx.x; i < G * HD; i += DEC_BLOCK) {
-        const int g = i / HD, d = i % HD;
-        q_s[i] = f2bf(
-            bf2f(q[(long)b * q_stride + (kvh * G + g) * (long)HD + d]) * scale);
+    // SCALED: the fp8 MFMA quantizes the staged q to e4m3 with no scale of
+    // its own, and a head whose K runs large has a correspondingly small q
+    // (logits stay O(1)) that would land in e4m3's subnormals or flush to
+    // zero. So when the block's staged q has amax < 2^-5 (at most one
+    // binade of it would be normal e4m3) the rows are brought into range by
+    // a power of two 2^k (exact on bf16: only the exponent moves) taken
+    // from that amax, amax * 2^k in [128, 256), and 2^-k joins k_scale in
+    // the one uniform factor applied to the fp32 scores. At or above 2^-5
+    // q is staged exactly as on the unscaled path, so there all-ones scales
+    // reproduce the unscaled output bit for bit.
+    if (SCALED) {
+        float amax = 0.f;
+        for (int i = threadIdx.x; i < G * HD; i += DEC_BLOCK) {
+            const int g = i / HD, d = i % HD;
+            amax = fmaxf(amax, fabsf(bf2f(f2bf(
+                bf2f(q[(long)b * q_stride + (kvh * G + g) * (long)HD + d]) *
+                scale))));
+        }
+        amax = wave_max(amax);
+        if (lane == 0) red[wid] = amax;
+        __syncthreads();
+        amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+        const int e = __builtin_amdgcn_readfirstlane(
+            (__float_as_int(amax) >> 23) & 0xff);
+        float qmul = 1.f;
+        if (e >= 8 && e < 122) {  // amax < 2^-5; 2^-k stays a normal float
+            qmul = __int_as_float((261 - e) << 23);  // 2^(134 - e)
+            ksc *= __int_as_float((e - 7) << 23);    // 2^(e - 134)
+        }
+        for (int i = threadIdx.x; i < G * HD; i += DEC_BLOCK) {
+            const int g = i / HD, d = i % HD;
+            q_s[i] = f2bf(bf2f(f2bf(
+                bf2f(q[(long)b * q_stride + (kvh * G + g) * (long)HD + d]) *
+                scale)) * qmul);
+        }
+    } else {
+        for (int i = threadIdx.x; i < G * HD; i += DEC_BLOCK) {
+            const int g = i / HD, d = i % HD;
+            q_s[i] = f2bf(bf2f(
+                q[(long)b * q_stride + (kvh * G + g) * (long)HD + d]) * scale);
+        }
     }
     __syncthreads();
 
@@ -361,7 +426,9 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_scores_mfma_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int key = wave_key0 + t * 16 + lg * 4 + r;
-            float v = (key < L) ? acc[t][r] : -1e30f;
+            // SCALED: per-head K dequant scale on the fp32 score
+            float v = (key < L) ? (SCALED ? acc[t][r] * ksc : acc[t][r])
+                                : -1e30f;
             sv[t * 4 + r] = v;
             lmax = fmaxf(lmax, v);
         }
@@ -444,13 +511,16 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_pv_kernel(
                                                  // the cross-rank merge
                                                  // state for context
                                                  // parallelism (parallel/cp)
-    int nkv, int W, int bs, int hd, int C) {
+    int nkv, int W, int bs, int hd, int C,
+    const float* __restrict__ v_scale) {         // [nkv] or nullptr
     const int b = blockIdx.x;
     const int kvh = blockIdx.y;
     const int L = seq_lens[b];
     if ((int)blockIdx.z * DEC_CHUNK >= L) return;
     const int lane = threadIdx.x % WAVE;
     const int wid = threadIdx.x / WAVE;
+    const bool scaled = sizeof(KVT) == 1 && v_scale != nullptr;
+    const float vsc = scaled ? v_scale[kvh] : 1.f;
 
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* p_s = reinterpret_cast<float*>(smem_raw);  // [CHUNK][G]
@@ -578,6 +648,10 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_pv_kernel(
                     runml[g * 2 + 1] = runml[g * 2 + 1] * alpha + lc * beta;
                 }
             } else {
+                if (scaled) {  // per-head V dequant scale, once
+                    a0 *= vsc;
+                    a1 *= vsc;
+                }
                 float* po = part_o + (base + g) * hd;
                 po[d0] = a0;
                 po[d0 + 1] = a1;
@@ -596,8 +670,14 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_pv_kernel(
                 const float inv = (lr > 0.f) ? 1.f / lr : 0.f;
                 unsigned short* orow =
                     out + ((long)b * nq + kvh * G + g) * hd;
-                orow[d0f] = f2bf(run[g * hd + d0f] * inv);
-                orow[d0f + 1] = f2bf(run[g * hd + d0f + 1] * inv);
+                float r0 = run[g * hd + d0f] * inv;
+                float r1 = run[g * hd + d0f + 1] * inv;
+                if (scaled) {  // per-head V dequant scale, once
+                    r0 *= vsc;
+                    r1 *= vsc;
+                }
+                orow[d0f] = f2bf(r0);
+                orow[d0f + 1] = f2bf(r1);
             }
         }
         if (out_ml != nullptr && lane == 0) {
@@ -797,13 +877,36 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_decode_combine_kernel(
     }
 }
 
+// MFMA scores launch: SCALED only exists for the fp8 cache type
+template <int G, int HD, typename KVT>
+static void launch_scores_mfma(
+    dim3 grid, int smem, hipStream_t stream, const unsigned short* q,
+    const KVT* kc, const int* block_table, const int* seq_lens,
+    unsigned short* p_buf, float* part_ml, int nkv, int W, int bs, int C,
+    long q_stride, float scale, const float* k_scale) {
+    if constexpr (sizeof(KVT) == 1) {
+        if (k_scale != nullptr) {
+            hipLaunchKernelGGL((attn_scores_mfma_kernel<G, HD, KVT, true>),
+                               grid, dim3(DEC_BLOCK), smem, stream, q, kc,
+                               block_table, seq_lens, p_buf, part_ml, nkv, W,
+                               bs, C, q_stride, scale, k_scale);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((attn_scores_mfma_kernel<G, HD, KVT, false>), grid,
+                       dim3(DEC_BLOCK), smem, stream, q, kc, block_table,
+                       seq_lens, p_buf, part_ml, nkv, W, bs, C, q_stride,
+                       scale, nullptr);
+}
+
 extern "C" void launch_attn_decode(
     const unsigned short* q, const void* k_cache, const void* v_cache,
     const int* block_table, const int* seq_lens, unsigned short* p_buf,
     float* part_o, float* part_ml, unsigned short* out, float* out_ml,
     int B, int nkv,
     int G, int W, int bs, int hd, int C, long q_stride, float scale,
-    int fp8, hipStream_t stream) {
+    int fp8, const float* k_scale, const float* v_scale,
+    hipStream_t stream) {
     // enough blocks to fill the chip, but chunks loop within a block so the
     // cold-start/tail phases amortize over multiple 64 KB K/V bursts
     int Z = (4096 + B * nkv - 1) / (B * nkv);
@@ -831,20 +934,20 @@ extern "C" void launch_attn_decode(
         const KVT* kc = reinterpret_cast<const KVT*>(k_cache);                 \
         const KVT* vc = reinterpret_cast<const KVT*>(v_cache);                 \
         if (hd == 128)                                                         \
-            hipLaunchKernelGGL((attn_scores_mfma_kernel<GG, 128, KVT>), grid,  \
-                               dim3(DEC_BLOCK), smem_s, stream, q, kc,         \
-                               block_table, seq_lens, p_buf, part_ml, nkv, W,  \
-                               bs, C, q_stride, scale);                        \
+            launch_scores_mfma<GG, 128, KVT>(grid, smem_s, stream, q, kc,      \
+                                             block_table, seq_lens, p_buf,     \
+                                             part_ml, nkv, W, bs, C, q_stride, \
+                                             scale, k_scale);                  \
         else if (hd == 64)                                                     \
-            hipLaunchKernelGGL((attn_scores_mfma_kernel<GG, 64, KVT>), grid,   \
-                               dim3(DEC_BLOCK), smem_s, stream, q, kc,         \
-                               block_table, seq_lens, p_buf, part_ml, nkv, W,  \
-                               bs, C, q_stride, scale);                        \
+            launch_scores_mfma<GG, 64, KVT>(grid, smem_s, stream, q, kc,       \
+                                            block_table, seq_lens, p_buf,      \
+                                            part_ml, nkv, W, bs, C, q_stride,  \
+                                            scale, k_scale);                   \
         else                                                                   \
             hipLaunchKernelGGL((attn_scores_kernel<GG, KVT>), grid,            \
                                dim3(DEC_BLOCK), smem_s, stream, q, kc,         \
                                block_table, seq_lens, p_buf, part_ml, nkv, W,  \
-                               bs, hd, C, q_stride, scale);                    \
+                               bs, hd, C, q_stride, scale, k_scale);           \
         if (hd == 128 && pv_mfma && !fp8) {                                    \
             hipLaunchKernelGGL(attn_pv_mfma_kernel<GG>, grid,                  \
                                dim3(DEC_BLOCK), smem_pvm, stream,              \
@@ -859,12 +962,13 @@ extern "C" void launch_attn_decode(
             hipLaunchKernelGGL((attn_pv_kernel<GG, true, KVT>), grid,          \
                                dim3(DEC_BLOCK), smem_pv, stream, vc,           \
                                block_table, seq_lens, p_buf, part_o, part_ml,  \
-                               out, out_ml, nkv, W, bs, hd, C);                \
+                               out, out_ml, nkv, W, bs, hd, C, v_scale);       \
         } else {                                                               \
             hipLaunchKernelGGL((attn_pv_kernel<GG, false, KVT>), grid,         \
                                dim3(DEC_BLOCK), smem_pv, stream, vc,           \
                                block_table, seq_lens, p_buf, part_o,           \
-                               part_ml, out, nullptr, nkv, W, bs, hd, C);      \
+                               part_ml, out, nullptr, nkv, W, bs, hd, C,       \
+                               v_scale);                                       \
             hipLaunchKernelGGL(attn_decode_combine_kernel<GG>, cgrid,          \
                                dim3(DEC_BLOCK), 0, stream, part_o, part_ml,    \
                                seq_lens, out, out_ml, nkv, hd, C);             \

@@ -18,6 +18,13 @@
 //    (test models): per (seq, head) workgroup, lanes-over-keys scores +
 //    lanes-over-dims PV like the decode kernel.
 //
+// Per-kv-head fp8 scales (PAGED + fp8 cache only; nullptr = unit): q stays
+// bf16 here, so k_scale folds into the softmax scale applied to q, and
+// v_scale folds into the epilogue's 1/l — the fp32 scores and the fp32
+// output accumulator are what get scaled, never each element at
+// dequant-to-LDS time. Both are scalar loads (kvh is block-uniform); the
+// bf16 instantiations compile the scale code away.
+//
 // Numerics reference: ops/reference.py attn_prefill.
 #include "common.h"
 
@@ -51,10 +58,17 @@ __global__ __launch_bounds__(64) void attn_prefill_basic(
     const int* __restrict__ seq_lens,      // PAGED only: total len incl chunk
     unsigned short* __restrict__ out,      // [T, nq, hd]
     int nq, int nkv, int hd, long s_q, long s_k, long s_v, int W, int bs,
-    float scale, int causal) {
+    float scale, int causal,
+    const float* __restrict__ k_scale,     // [nkv] or nullptr (fp8 only)
+    const float* __restrict__ v_scale) {
     const int seq = blockIdx.y;
     const int h = blockIdx.x;
     const int kvh = h / (nq / nkv);
+    float vsc = 1.f;
+    if (sizeof(KVT) == 1 && k_scale != nullptr) {
+        scale *= k_scale[kvh];
+        vsc = v_scale[kvh];
+    }
     const int s0 = cu[seq], s1 = cu[seq + 1];
     const int QL = s1 - s0;
     const int L = PAGED ? seq_lens[seq] : QL;
@@ -112,7 +126,7 @@ __global__ __launch_bounds__(64) void attn_prefill_basic(
             }
         }
         if (d0 < hd) {
-            const float inv = (lsum > 0.f) ? 1.f / lsum : 0.f;
+            const float inv = (lsum > 0.f) ? (1.f / lsum) * vsc : 0.f;
             unsigned short* orow = out + ((long)(s0 + r) * nq + h) * hd;
             orow[d0] = f2bf(o0 * inv);
             orow[d0 + 1] = f2bf(o1 * inv);
@@ -143,11 +157,18 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma(
     const int* __restrict__ seq_lens,      // PAGED only
     unsigned short* __restrict__ out,
     int nq, int nkv, long s_q, long s_k, long s_v, int W, int bs,
-    float scale) {
+    float scale,
+    const float* __restrict__ k_scale,     // [nkv] or nullptr (fp8 only)
+    const float* __restrict__ v_scale) {
     constexpr int KSTEPS = HD / 32;
     const int seq = blockIdx.z;
     const int h = blockIdx.y;
     const int kvh = h / (nq / nkv);
+    float vsc = 1.f;
+    if (sizeof(KVT) == 1 && k_scale != nullptr) {
+        scale *= k_scale[kvh];
+        vsc = v_scale[kvh];
+    }
     const int s0 = cu[seq], s1 = cu[seq + 1];
     const int QL = s1 - s0;                // query rows in this chunk
     const int L = PAGED ? seq_lens[seq] : QL;  // keys incl. cached history
@@ -344,7 +365,7 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma(
     for (int r = 0; r < 4; ++r) {
         const int qrow = orow_base + lg * 4 + r;
         if (qrow >= QL) continue;
-        const float inv = (l_run[r] > 0.f) ? 1.f / l_run[r] : 0.f;
+        const float inv = (l_run[r] > 0.f) ? (1.f / l_run[r]) * vsc : 0.f;
         unsigned short* orow = out + ((long)(s0 + qrow) * nq + h) * HD;
 #pragma unroll
         for (int nb = 0; nb < HD / 16; ++nb)
@@ -373,12 +394,12 @@ extern "C" void launch_attn_prefill(
             hipLaunchKernelGGL((attn_prefill_mfma<128, false, unsigned short>),
                                grid, dim3(256), smem, stream, q, k, v, cu,
                                nullptr, nullptr, out, nq, nkv, s_q, s_k, s_v,
-                               0, 0, scale);
+                               0, 0, scale, nullptr, nullptr);
         else
             hipLaunchKernelGGL((attn_prefill_mfma<64, false, unsigned short>),
                                grid, dim3(256), smem, stream, q, k, v, cu,
                                nullptr, nullptr, out, nq, nkv, s_q, s_k, s_v,
-                               0, 0, scale);
+                               0, 0, scale, nullptr, nullptr);
         return;
     }
     dim3 grid(nq, nseq);
@@ -386,7 +407,7 @@ extern "C" void launch_attn_prefill(
     hipLaunchKernelGGL((attn_prefill_basic<false, unsigned short>), grid,
                        dim3(WAVE), smem, stream, q, k, v, cu, nullptr,
                        nullptr, out, nq, nkv, hd, s_q, s_k, s_v, 0, 0, scale,
-                       causal);
+                       causal, nullptr, nullptr);
 }
 
 // Chunked prefill: query chunks (packed varlen, cu) attend to the full
@@ -396,7 +417,8 @@ extern "C" void launch_attn_prefill_paged(
     const unsigned short* q, const void* k_cache, const void* v_cache,
     const int* cu, const int* block_table, const int* seq_lens,
     unsigned short* out, int nseq, int nq, int nkv, int hd, long s_q, int W,
-    int bs, int max_qlen, float scale, int fp8, hipStream_t stream) {
+    int bs, int max_qlen, float scale, int fp8, const float* k_scale,
+    const float* v_scale, hipStream_t stream) {
 #define PFP_LAUNCH(KVT)                                                        \
     do {                                                                       \
         const KVT* kc = reinterpret_cast<const KVT*>(k_cache);                 \
@@ -409,19 +431,20 @@ extern "C" void launch_attn_prefill_paged(
                 hipLaunchKernelGGL((attn_prefill_mfma<128, true, KVT>), grid,  \
                                    dim3(256), smem, stream, q, kc, vc, cu,     \
                                    block_table, seq_lens, out, nq, nkv, s_q,   \
-                                   0, 0, W, bs, scale);                        \
+                                   0, 0, W, bs, scale, k_scale, v_scale);      \
             else                                                               \
                 hipLaunchKernelGGL((attn_prefill_mfma<64, true, KVT>), grid,   \
                                    dim3(256), smem, stream, q, kc, vc, cu,     \
                                    block_table, seq_lens, out, nq, nkv, s_q,   \
-                                   0, 0, W, bs, scale);                        \
+                                   0, 0, W, bs, scale, k_scale, v_scale);      \
             return;                                                            \
         }                                                                      \
         dim3 grid(nq, nseq);                                                   \
         const int smem = (hd + WAVE) * 4;                                      \
         hipLaunchKernelGGL((attn_prefill_basic<true, KVT>), grid, dim3(WAVE),  \
                            smem, stream, q, kc, vc, cu, block_table, seq_lens, \
-                           out, nq, nkv, hd, s_q, 0, 0, W, bs, scale, 1);      \
+                           out, nq, nkv, hd, s_q, 0, 0, W, bs, scale, 1,       \
+                           k_scale, v_scale);                                  \
     } while (0)
     if (fp8) PFP_LAUNCH(unsigned char);
     else PFP_LAUNCH(unsigned short);

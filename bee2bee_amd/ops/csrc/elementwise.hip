@@ -213,14 +213,26 @@ __global__ void kv_store_kernel(
 }
 
 // fp8 (OCP e4m3) KV cache variant: quantize at store time (RNE pack), so
-// the decode kernels read HALF the bytes. Scale is 1.0 (e4m3 covers +-448;
-// post-RMSNorm K/V magnitudes sit well inside — opt-in, documented).
+// the decode kernels read HALF the bytes. With k_inv/v_inv == nullptr the
+// scale is 1.0 (e4m3 covers +-448; post-RMSNorm K/V magnitudes sit well
+// inside). With per-kv-head reciprocal scales ([nkv] fp32, both given):
+//   byte = e4m3_rne(clamp(x * inv_scale[h], -448, 448))
+// The clamp is explicit so the byte never depends on the convert
+// instruction's overflow mode; the reciprocal comes from the host, so
+// there is no device-side division. h is wave-uniform (one wave per
+// (token, head)), so the two scales are scalar loads.
+__device__ __forceinline__ float clamp_e4m3(float x) {
+    return fminf(fmaxf(x, -448.f), 448.f);
+}
+
 __global__ void kv_store_fp8_kernel(
     const unsigned short* __restrict__ k,  // [T, nkv, hd] bf16
     const unsigned short* __restrict__ v,
     unsigned char* __restrict__ k_cache,   // [nb, nkv, bs, hd] fp8
     unsigned char* __restrict__ v_cache,
     const int* __restrict__ slots,
+    const float* __restrict__ k_inv,       // [nkv] or nullptr (unit scale)
+    const float* __restrict__ v_inv,
     int T, int nkv, int hd, int bs, long sk, long sv) {
     const int glob_wave = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
     const int lane = threadIdx.x % WAVE;
@@ -232,6 +244,21 @@ __global__ void kv_store_fp8_kernel(
     const long dst = (((long)blk * nkv + h) * bs + off) * hd;
     const unsigned short* ks = k + (long)t * sk + (long)h * hd;
     const unsigned short* vs = v + (long)t * sv + (long)h * hd;
+    if (k_inv != nullptr) {
+        const int hu = __builtin_amdgcn_readfirstlane(h);
+        const float ki = k_inv[hu], vi = v_inv[hu];
+        for (int d = lane * 2; d + 1 < hd; d += WAVE * 2) {
+            const short2v kk = *reinterpret_cast<const short2v*>(ks + d);
+            const short2v vv = *reinterpret_cast<const short2v*>(vs + d);
+            *reinterpret_cast<unsigned short*>(k_cache + dst + d) = f2fp8x2(
+                clamp_e4m3(bf2f((unsigned short)kk[0]) * ki),
+                clamp_e4m3(bf2f((unsigned short)kk[1]) * ki));
+            *reinterpret_cast<unsigned short*>(v_cache + dst + d) = f2fp8x2(
+                clamp_e4m3(bf2f((unsigned short)vv[0]) * vi),
+                clamp_e4m3(bf2f((unsigned short)vv[1]) * vi));
+        }
+        return;
+    }
     for (int d = lane * 2; d + 1 < hd; d += WAVE * 2) {
         const short2v kk = *reinterpret_cast<const short2v*>(ks + d);
         const short2v vv = *reinterpret_cast<const short2v*>(vs + d);
@@ -336,13 +363,14 @@ void launch_kv_store(const unsigned short* k, const unsigned short* v,
 
 void launch_kv_store_fp8(const unsigned short* k, const unsigned short* v,
                          unsigned char* k_cache, unsigned char* v_cache,
-                         const int* slots, int T, int nkv, int hd, int bs,
+                         const int* slots, const float* k_inv,
+                         const float* v_inv, int T, int nkv, int hd, int bs,
                          long sk, long sv, hipStream_t stream) {
     const long waves = (long)T * nkv;
     const long blocks = (waves + 3) / 4;
     hipLaunchKernelGGL(kv_store_fp8_kernel, dim3(blocks), dim3(256), 0,
-                       stream, k, v, k_cache, v_cache, slots, T, nkv, hd, bs,
-                       sk, sv);
+                       stream, k, v, k_cache, v_cache, slots, k_inv, v_inv, T,
+                       nkv, hd, bs, sk, sv);
 }
 
 void launch_swiglu(const unsigned short* gu, unsigned short* out, long T,

@@ -29,14 +29,16 @@ void launch_kv_store(const unsigned short*, const unsigned short*,
                      unsigned short*, unsigned short*, const int*, int, int,
                      int, int, long, long, hipStream_t);
 void launch_kv_store_fp8(const unsigned short*, const unsigned short*,
-                         unsigned char*, unsigned char*, const int*, int,
-                         int, int, int, long, long, hipStream_t);
+                         unsigned char*, unsigned char*, const int*,
+                         const float*, const float*, int, int, int, int, long,
+                         long, hipStream_t);
 void launch_swiglu(const unsigned short*, unsigned short*, long, long,
                    hipStream_t);
 void launch_attn_decode(const unsigned short*, const void*, const void*,
                         const int*, const int*, unsigned short*, float*,
                         float*, unsigned short*, float*, int, int, int, int,
-                        int, int, int, long, float, int, hipStream_t);
+                        int, int, int, long, float, int, const float*,
+                        const float*, hipStream_t);
 void launch_attn_prefill(const unsigned short*, const unsigned short*,
                          const unsigned short*, const int*, unsigned short*,
                          int, int, int, int, long, long, long, int, float,
@@ -45,7 +47,7 @@ void launch_attn_prefill_paged(const unsigned short*, const void*,
                                const void*, const int*, const int*,
                                const int*, unsigned short*, int, int, int,
                                int, long, int, int, int, float, int,
-                               hipStream_t);
+                               const float*, const float*, hipStream_t);
 void launch_mfma_probe(const unsigned short*, const unsigned short*, float*,
                        hipStream_t);
 void launch_mfma_probe_fp8(const unsigned char*, const unsigned char*,
@@ -69,6 +71,28 @@ inline hipStream_t stream() {
 }
 
 inline bool hd_fp8_ok(long hd) { return hd % 8 == 0; }
+
+using OptTensor = c10::optional<Tensor>;
+
+// Per-kv-head fp8 scales: both given or neither; fp32 [nkv] contiguous on
+// the cache's device; only meaningful for a uint8 (fp8) cache. Returns
+// true when scales are present.
+bool check_kv_scales(const OptTensor& a, const OptTensor& b,
+                     const Tensor& cache, const char* what) {
+    TORCH_CHECK(a.has_value() == b.has_value(), what,
+                ": give both K and V scales or neither");
+    if (!a.has_value()) return false;
+    TORCH_CHECK(cache.scalar_type() == torch::kUInt8, what,
+                ": per-head KV scales need an fp8 (uint8) cache");
+    for (const Tensor* t : {&*a, &*b}) {
+        TORCH_CHECK(t->is_cuda() && t->device() == cache.device(), what,
+                    ": scales must be on the cache's device");
+        TORCH_CHECK(t->scalar_type() == torch::kFloat32 && t->dim() == 1 &&
+                        t->size(0) == cache.size(1) && t->is_contiguous(),
+                    what, ": scales must be fp32 [n_kv_heads] contiguous");
+    }
+    return true;
+}
 
 inline const unsigned short* bf16p(const Tensor& t) {
     return reinterpret_cast<const unsigned short*>(t.data_ptr());
@@ -132,8 +156,12 @@ void rope_inplace(Tensor& q, Tensor& k, const Tensor& pos, const Tensor& cos_t,
 }
 
 void kv_cache_store(const Tensor& k, const Tensor& v, Tensor& k_cache,
-                    Tensor& v_cache, const Tensor& slots) {
+                    Tensor& v_cache, const Tensor& slots,
+                    const OptTensor& k_inv_scale,
+                    const OptTensor& v_inv_scale) {
     check_bf16(k, "k");
+    const bool scaled =
+        check_kv_scales(k_inv_scale, v_inv_scale, k_cache, "kv_cache_store");
     TORCH_CHECK(slots.scalar_type() == torch::kInt32);
     const int T = k.size(0), nkv = k.size(1), hd = k.size(2);
     const int bs = k_cache.size(2);
@@ -147,8 +175,11 @@ void kv_cache_store(const Tensor& k, const Tensor& v, Tensor& k_cache,
         launch_kv_store_fp8(bf16p(k), bf16p(v),
                             k_cache.data_ptr<unsigned char>(),
                             v_cache.data_ptr<unsigned char>(),
-                            slots.data_ptr<int>(), T, nkv, hd, bs,
-                            k.stride(0), v.stride(0), stream());
+                            slots.data_ptr<int>(),
+                            scaled ? k_inv_scale->data_ptr<float>() : nullptr,
+                            scaled ? v_inv_scale->data_ptr<float>() : nullptr,
+                            T, nkv, hd, bs, k.stride(0), v.stride(0),
+                            stream());
         return;
     }
     check_bf16(k_cache, "k_cache");
@@ -214,8 +245,12 @@ std::vector<Tensor> attn_decode_impl(const Tensor& q, const Tensor& k_cache,
                                      const Tensor& v_cache,
                                      const Tensor& block_table,
                                      const Tensor& seq_lens, double scale,
+                                     const OptTensor& k_scale,
+                                     const OptTensor& v_scale,
                                      bool want_lse) {
     check_bf16(q, "q");
+    const bool scaled =
+        check_kv_scales(k_scale, v_scale, k_cache, "attn_decode");
     const bool fp8 = k_cache.scalar_type() == torch::kUInt8;
     if (!fp8) check_bf16(k_cache, "k_cache");
     TORCH_CHECK(fp8 ? hd_fp8_ok(q.size(2)) : true,
@@ -252,16 +287,20 @@ std::vector<Tensor> attn_decode_impl(const Tensor& q, const Tensor& k_cache,
                        bf16p_mut(p_buf), part_o.data_ptr<float>(),
                        part_ml.data_ptr<float>(),
                        bf16p_mut(out), out_ml_p, B, nkv, G, W, bs, hd, C,
-                       q.stride(0), (float)scale, fp8 ? 1 : 0, stream());
+                       q.stride(0), (float)scale, fp8 ? 1 : 0,
+                       scaled ? k_scale->data_ptr<float>() : nullptr,
+                       scaled ? v_scale->data_ptr<float>() : nullptr,
+                       stream());
     if (want_lse) return {out, out_ml};
     return {out};
 }
 
 Tensor attn_decode(const Tensor& q, const Tensor& k_cache,
                    const Tensor& v_cache, const Tensor& block_table,
-                   const Tensor& seq_lens, double scale) {
+                   const Tensor& seq_lens, double scale,
+                   const OptTensor& k_scale, const OptTensor& v_scale) {
     return attn_decode_impl(q, k_cache, v_cache, block_table, seq_lens,
-                            scale, false)[0];
+                            scale, k_scale, v_scale, false)[0];
 }
 
 // out + per-(seq, q-head) (m, l): the flash merge state that context
@@ -269,9 +308,11 @@ Tensor attn_decode(const Tensor& q, const Tensor& k_cache,
 std::vector<Tensor> attn_decode_lse(const Tensor& q, const Tensor& k_cache,
                                     const Tensor& v_cache,
                                     const Tensor& block_table,
-                                    const Tensor& seq_lens, double scale) {
+                                    const Tensor& seq_lens, double scale,
+                                    const OptTensor& k_scale,
+                                    const OptTensor& v_scale) {
     return attn_decode_impl(q, k_cache, v_cache, block_table, seq_lens,
-                            scale, true);
+                            scale, k_scale, v_scale, true);
 }
 
 Tensor attn_prefill(const Tensor& q, const Tensor& k, const Tensor& v,
@@ -300,8 +341,12 @@ Tensor attn_prefill(const Tensor& q, const Tensor& k, const Tensor& v,
 Tensor attn_prefill_paged(const Tensor& q, const Tensor& k_cache,
                           const Tensor& v_cache, const Tensor& block_table,
                           const Tensor& seq_lens, const Tensor& cu_q,
-                          long max_qlen, double scale) {
+                          long max_qlen, double scale,
+                          const OptTensor& k_scale,
+                          const OptTensor& v_scale) {
     check_bf16(q, "q");
+    const bool scaled =
+        check_kv_scales(k_scale, v_scale, k_cache, "attn_prefill_paged");
     const bool fp8 = k_cache.scalar_type() == torch::kUInt8;
     if (!fp8) check_bf16(k_cache, "k_cache");
     TORCH_CHECK(block_table.scalar_type() == torch::kInt32 &&
@@ -323,7 +368,10 @@ Tensor attn_prefill_paged(const Tensor& q, const Tensor& k_cache,
                               block_table.data_ptr<int>(),
                               seq_lens.data_ptr<int>(), bf16p_mut(out), nseq,
                               nq, nkv, hd, q.stride(0), W, bs, (int)max_qlen,
-                              (float)scale, fp8 ? 1 : 0, stream());
+                              (float)scale, fp8 ? 1 : 0,
+                              scaled ? k_scale->data_ptr<float>() : nullptr,
+                              scaled ? v_scale->data_ptr<float>() : nullptr,
+                              stream());
     return out;
 }
 
@@ -400,18 +448,32 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("fused_add_rmsnorm", &fused_add_rmsnorm,
           "residual += x; y = rmsnorm(residual)");
     m.def("rope_inplace", &rope_inplace, "llama RoPE in place");
-    m.def("kv_cache_store", &kv_cache_store, "paged KV scatter");
+    namespace py = pybind11;
+    m.def("kv_cache_store", &kv_cache_store, "paged KV scatter",
+          py::arg("k"), py::arg("v"), py::arg("k_cache"), py::arg("v_cache"),
+          py::arg("slots"), py::arg("k_inv_scale") = py::none(),
+          py::arg("v_inv_scale") = py::none());
     m.def("swiglu", &swiglu, "silu(g) * u");
     m.def("layernorm", &layernorm, "LayerNorm (bf16, weight+bias)");
     m.def("fused_add_layernorm", &fused_add_layernorm,
           "residual add + LayerNorm");
     m.def("gelu", &gelu, "gelu_new (tanh approximation)");
-    m.def("attn_decode", &attn_decode, "paged GQA decode attention");
+    m.def("attn_decode", &attn_decode, "paged GQA decode attention",
+          py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+          py::arg("block_table"), py::arg("seq_lens"), py::arg("scale"),
+          py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
     m.def("attn_decode_lse", &attn_decode_lse,
-          "paged GQA decode attention + per-head (m, l) merge state");
+          "paged GQA decode attention + per-head (m, l) merge state",
+          py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+          py::arg("block_table"), py::arg("seq_lens"), py::arg("scale"),
+          py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
     m.def("attn_prefill", &attn_prefill, "varlen causal flash prefill");
     m.def("attn_prefill_paged", &attn_prefill_paged,
-          "chunked prefill vs paged history");
+          "chunked prefill vs paged history", py::arg("q"),
+          py::arg("k_cache"), py::arg("v_cache"), py::arg("block_table"),
+          py::arg("seq_lens"), py::arg("cu_q"), py::arg("max_qlen"),
+          py::arg("scale"), py::arg("k_scale") = py::none(),
+          py::arg("v_scale") = py::none());
     m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
     m.def("mfma_probe_fp8", &mfma_probe_fp8,
           "16x16x32 fp8 MFMA layout probe");

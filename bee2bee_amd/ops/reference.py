@@ -124,18 +124,54 @@ def _kv_quant_like(x: torch.Tensor, cache: torch.Tensor) -> torch.Tensor:
     return x.to(cache.dtype)
 
 
+E4M3_MAX = 448.0
+
+
+def _kv_quant_scaled(x: torch.Tensor, inv_scale: torch.Tensor) -> torch.Tensor:
+    """Per-kv-head scaled fp8 quantization, the definition the HIP store
+    kernel follows: byte = e4m3_rne(clamp(x * inv_scale[h], -448, 448)) in
+    fp32. x [T, n_kv, hd], inv_scale [n_kv]."""
+    y = x.float() * inv_scale.float().view(1, -1, 1)
+    y = y.clamp(-E4M3_MAX, E4M3_MAX)
+    return y.to(torch.float8_e4m3fn).view(torch.uint8)
+
+
+def _check_scales(cache: torch.Tensor, *scales) -> None:
+    for s in scales:
+        if s is None:
+            continue
+        if cache.dtype != torch.uint8:
+            raise ValueError("per-head KV scales need an fp8 (uint8) cache")
+        if s.dtype != torch.float32 or s.shape != (cache.shape[1],):
+            raise ValueError("KV scales must be fp32 [n_kv_heads]")
+
+
+def _head_scale(x: torch.Tensor, s) -> torch.Tensor:
+    """x [n_kv, ...] times the per-kv-head scale s [n_kv] (None: unit)."""
+    if s is None:
+        return x
+    return x * s.float().view(-1, *([1] * (x.dim() - 1)))
+
+
 def kv_cache_store(
     k: torch.Tensor,
     v: torch.Tensor,
     k_cache: torch.Tensor,
     v_cache: torch.Tensor,
     slot_mapping: torch.Tensor,
+    k_inv_scale: torch.Tensor = None,
+    v_inv_scale: torch.Tensor = None,
 ) -> None:
     n_blocks, n_kv, block_size, hd = k_cache.shape
+    _check_scales(k_cache, k_inv_scale, v_inv_scale)
     blk = torch.div(slot_mapping, block_size, rounding_mode="floor").long()
     off = (slot_mapping % block_size).long()
-    k_cache[blk, :, off, :] = _kv_quant_like(k, k_cache)
-    v_cache[blk, :, off, :] = _kv_quant_like(v, v_cache)
+    k_cache[blk, :, off, :] = (
+        _kv_quant_like(k, k_cache) if k_inv_scale is None
+        else _kv_quant_scaled(k, k_inv_scale))
+    v_cache[blk, :, off, :] = (
+        _kv_quant_like(v, v_cache) if v_inv_scale is None
+        else _kv_quant_scaled(v, v_inv_scale))
 
 
 def attn_decode(
@@ -146,13 +182,19 @@ def attn_decode(
     seq_lens: torch.Tensor,
     scale: float,
     out_ml: torch.Tensor = None,
+    k_scale: torch.Tensor = None,
+    v_scale: torch.Tensor = None,
 ) -> torch.Tensor:
     """Paged single-token attention, GQA. q [B, nq, hd] -> out [B, nq, hd].
     When out_ml [B, nq, 2] is given, also writes the flash merge state
     (max scaled score m, sum-exp l) per query head — the cross-rank
-    exchange for context parallelism."""
+    exchange for context parallelism. k_scale / v_scale [n_kv] are the
+    per-kv-head dequantization scales of a scaled fp8 cache: the scores
+    (and so m, l) are taken on float(byte) * k_scale, the output on
+    float(byte) * v_scale."""
     B, nq, hd = q.shape
     _nb, n_kv, block_size, _ = k_cache.shape
+    _check_scales(k_cache, k_scale, v_scale)
     group = nq // n_kv
     out = torch.empty_like(q)
     for b in range(B):
@@ -173,8 +215,9 @@ def attn_decode(
         vals = vals.permute(1, 0, 2, 3).reshape(n_kv, nblk * block_size, hd)[:, :L]
         qb = q[b].float().view(n_kv, group, hd)
         scores = torch.einsum("kgd,kld->kgl", qb, keys) * scale
+        scores = _head_scale(scores, k_scale)
         probs = torch.softmax(scores, dim=-1)
-        ob = torch.einsum("kgl,kld->kgd", probs, vals)
+        ob = _head_scale(torch.einsum("kgl,kld->kgd", probs, vals), v_scale)
         out[b] = ob.reshape(nq, hd).to(q.dtype)
         if out_ml is not None:
             m = scores.amax(dim=-1)                         # [n_kv, group]
@@ -224,6 +267,8 @@ def attn_decode_with_history(
     seq_lens: torch.Tensor,
     query_lens: torch.Tensor,
     scale: float,
+    k_scale: torch.Tensor = None,
+    v_scale: torch.Tensor = None,
 ) -> torch.Tensor:
     """Chunked-prefill attention: multiple new query tokens per sequence
     attending to the full paged history (new tokens already stored in cache).
@@ -233,6 +278,7 @@ def attn_decode_with_history(
     T, nq, hd = q.shape
     _nb, n_kv, block_size, _ = k_cache.shape
     group = nq // n_kv
+    _check_scales(k_cache, k_scale, v_scale)
     out = torch.empty_like(q)
     t0 = 0
     for b in range(query_lens.numel()):
@@ -250,12 +296,14 @@ def attn_decode_with_history(
         )
         qb = q[t0 : t0 + QL].float().view(QL, n_kv, group, hd)
         scores = torch.einsum("qkgd,kld->kgql", qb, keys) * scale
+        scores = _head_scale(scores, k_scale)
         # causal within the chunk: query j (absolute pos L-QL+j) sees keys <= pos
         qpos = torch.arange(L - QL, L, device=q.device).view(1, 1, QL, 1)
         kpos = torch.arange(L, device=q.device).view(1, 1, 1, L)
         scores.masked_fill_(kpos > qpos, float("-inf"))
         probs = torch.softmax(scores, dim=-1)
-        ob = torch.einsum("kgql,kld->qkgd", probs, vals)
+        ob = torch.einsum("kgql,kld->kgqd", probs, vals)
+        ob = _head_scale(ob, v_scale).permute(2, 0, 1, 3)
         out[t0 : t0 + QL] = ob.reshape(QL, nq, hd).to(q.dtype)
         t0 += QL
     return out
@@ -299,10 +347,12 @@ def attn_decode_lse(
     block_table: torch.Tensor,
     seq_lens: torch.Tensor,
     scale: float,
+    k_scale: torch.Tensor = None,
+    v_scale: torch.Tensor = None,
 ):
     """attn_decode + per-head (m, l) merge state (see parallel/cp.py)."""
     out_ml = torch.empty(q.shape[0], q.shape[1], 2, dtype=torch.float32,
                          device=q.device)
     out = attn_decode(q, k_cache, v_cache, block_table, seq_lens, scale,
-                      out_ml=out_ml)
+                      out_ml=out_ml, k_scale=k_scale, v_scale=v_scale)
     return out, out_ml

@@ -78,6 +78,8 @@ def cp_attn_decode(
     local_seq_lens: torch.Tensor,
     scale: float,
     group: Optional[dist.ProcessGroup] = None,
+    k_scale: Optional[torch.Tensor] = None,
+    v_scale: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Decode attention over a context sharded across the group's ranks.
 
@@ -87,7 +89,8 @@ def cp_attn_decode(
     assert dist.is_initialized(), "init the process group first"
     world = dist.get_world_size(group)
     out, ml = ops.attn_decode_lse(
-        q, k_cache, v_cache, local_block_table, local_seq_lens, scale)
+        q, k_cache, v_cache, local_block_table, local_seq_lens, scale,
+        k_scale=k_scale, v_scale=v_scale)
     # a rank with an empty shard produces garbage rows; zero their weight
     empty = (local_seq_lens == 0)
     if bool(empty.any()):
@@ -206,9 +209,11 @@ class CPEngine:
                 out.append(scratch)
         return out
 
-    def _cp_attn(self, q, k_cache, v_cache, block_table, seq_lens, scale):
+    def _cp_attn(self, q, k_cache, v_cache, block_table, seq_lens, scale,
+                 k_scale=None, v_scale=None):
         return cp_attn_decode(q, k_cache, v_cache, block_table, seq_lens,
-                              scale, group=self.group)
+                              scale, group=self.group, k_scale=k_scale,
+                              v_scale=v_scale)
 
     def _local_lens_t(self) -> torch.Tensor:
         return torch.tensor([self._local_len(L) for L in self._lens],

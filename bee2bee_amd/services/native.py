@@ -49,6 +49,14 @@ class NativeEngineService(BaseService):
         try:
             from ..engine.engine import InferenceEngine
 
+            kv_fp8 = os.environ.get("BEE2BEE_KV_FP8") == "1"
+            # per-head fp8 KV scales: PATH | checkpoint | calibrate
+            kv_scales = os.environ.get("BEE2BEE_KV_SCALES") or None
+            if kv_scales and not kv_fp8:
+                raise ValueError(
+                    "BEE2BEE_KV_SCALES is set but the fp8 KV cache is off: "
+                    "set BEE2BEE_KV_FP8=1 (--kv-fp8) as well")
+            calibrate = kv_scales == "calibrate"
             self.engine = InferenceEngine(
                 self.model_name,
                 device=self.device,
@@ -60,9 +68,17 @@ class NativeEngineService(BaseService):
                 spec_decode=os.environ.get("BEE2BEE_SPEC_DECODE") == "1",
                 # fp8 (OCP e4m3) KV pool: halves decode-attention bytes at a
                 # small quantization cost; serving opt-in
-                kv_dtype="fp8" if os.environ.get("BEE2BEE_KV_FP8") == "1"
-                else "native",
+                kv_dtype="fp8" if kv_fp8 else "native",
+                kv_scales=None if calibrate else kv_scales,
             )
+            if calibrate:
+                from ..engine.engine import default_calibration_prompts
+
+                self.engine.calibrate_kv_scales(
+                    default_calibration_prompts(self.engine))
+                out = os.environ.get("BEE2BEE_KV_SCALES_OUT")
+                if out:
+                    self.engine.save_kv_scales(out)
             self.engine.start()
         except Exception as e:
             raise ServiceError(f"failed to load model: {e}") from e

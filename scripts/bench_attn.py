@@ -27,7 +27,12 @@ def main():
                     help="bench the MFMA prefill kernel instead")
     ap.add_argument("--fp8", action="store_true",
                     help="fp8 (e4m3) KV cache variant of the decode bench")
+    ap.add_argument("--fp8-scaled", action="store_true",
+                    help="the --fp8 bench with non-unit per-kv-head scales "
+                         "passed (scaled scores / PV kernels)")
     args = ap.parse_args()
+    if args.fp8_scaled:
+        args.fp8 = True
 
     from bee2bee_amd import ops
 
@@ -73,18 +78,25 @@ def main():
     q = torch.randn(B, nq, hd, device=dev).bfloat16()
     lens = torch.full((B,), L, dtype=torch.int32, device=dev)
     scale = hd**-0.5
+    kw = {}
+    if args.fp8_scaled:
+        kw = {
+            "k_scale": torch.linspace(0.02, 0.08, nkv, device=dev),
+            "v_scale": torch.linspace(0.5, 2.0, nkv, device=dev),
+        }
 
     for _ in range(5):
-        out = ops.attn_decode(q, kc, vc, bt, lens, scale)
+        out = ops.attn_decode(q, kc, vc, bt, lens, scale, **kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.iters):
-        out = ops.attn_decode(q, kc, vc, bt, lens, scale)
+        out = ops.attn_decode(q, kc, vc, bt, lens, scale, **kw)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.iters
     kv_bytes = B * L * 2 * nkv * hd * (1 if args.fp8 else 2)
     print(
-        f"decode{' fp8' if args.fp8 else ''} "
+        f"decode{' fp8' if args.fp8 else ''}"
+        f"{'-scaled' if args.fp8_scaled else ''} "
         f"B{B} L{L} nkv{nkv} G{G} hd{hd}: {dt * 1e6:.1f} us  "
         f"KV {kv_bytes / 1e6:.0f} MB  {kv_bytes / dt / 1e12:.2f} TB/s"
     )
