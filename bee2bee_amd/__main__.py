@@ -35,6 +35,23 @@ _KV_SCALES_HELP = ("per-head fp8 KV scales: a scales file PATH, 'checkpoint' "
                    "(k_scale/v_scale tensors of the HF checkpoint) or "
                    "'calibrate' (measure at start-up); needs --kv-fp8")
 _KV_SCALES_OUT_HELP = "with --kv-scales calibrate: save the scales to PATH"
+_MAX_SEQ_LEN_HELP = "longest servable context in tokens (engine default 4096)"
+_SLIDING_WINDOW_HELP = ("sliding-window attention over the last N keys; 0 "
+                        "forces it off (default: the checkpoint's / preset's "
+                        "sliding_window). No effect when N >= --max-seq-len")
+
+
+def _ctx_env(max_seq_len, sliding_window) -> None:
+    """Hand --max-seq-len / --sliding-window to the native service through
+    their env twins (BEE2BEE_MAX_SEQ_LEN / BEE2BEE_SLIDING_WINDOW)."""
+    if max_seq_len is not None:
+        if max_seq_len < 2:
+            raise click.UsageError("--max-seq-len must be at least 2")
+        os.environ["BEE2BEE_MAX_SEQ_LEN"] = str(max_seq_len)
+    if sliding_window is not None:
+        if sliding_window < 0:
+            raise click.UsageError("--sliding-window must be >= 0")
+        os.environ["BEE2BEE_SLIDING_WINDOW"] = str(sliding_window)
 
 
 def _kv_env(kv_fp8: bool, kv_scales, kv_scales_out) -> None:
@@ -67,13 +84,17 @@ def _kv_env(kv_fp8: bool, kv_scales, kv_scales_out) -> None:
               help=_KV_SCALES_HELP)
 @click.option("--kv-scales-out", default=None, metavar="PATH",
               help=_KV_SCALES_OUT_HELP)
+@click.option("--max-seq-len", default=None, type=int, help=_MAX_SEQ_LEN_HELP)
+@click.option("--sliding-window", default=None, type=int, metavar="N",
+              help=_SLIDING_WINDOW_HELP)
 def serve_hf(model, model_path, port, region, api_port, device, kv_fp8,
-             kv_scales, kv_scales_out):
+             kv_scales, kv_scales_out, max_seq_len, sliding_window):
     """Serve a model on the native MI355X engine (HF-checkpoint compatible).
 
     Named serve-hf for reference-CLI compatibility; the execution engine is
     the hand-written CDNA4 HIP runtime, not transformers."""
     _kv_env(kv_fp8, kv_scales, kv_scales_out)
+    _ctx_env(max_seq_len, sliding_window)
     _serve(
         "native",
         model_name=model,
@@ -100,12 +121,17 @@ def serve_hf(model, model_path, port, region, api_port, device, kv_fp8,
               help=_KV_SCALES_HELP)
 @click.option("--kv-scales-out", default=None, metavar="PATH",
               help=_KV_SCALES_OUT_HELP)
+@click.option("--max-seq-len", default=None, type=int, help=_MAX_SEQ_LEN_HELP)
+@click.option("--sliding-window", default=None, type=int, metavar="N",
+              help=_SLIDING_WINDOW_HELP)
 def serve_native(model, model_path, port, region, api_port, device,
-                 spec_decode, kv_fp8, kv_scales, kv_scales_out):
+                 spec_decode, kv_fp8, kv_scales, kv_scales_out, max_seq_len,
+                 sliding_window):
     """Serve a model on the native MI355X HIP engine (alias of serve-hf)."""
     if spec_decode:
         os.environ["BEE2BEE_SPEC_DECODE"] = "1"
     _kv_env(kv_fp8, kv_scales, kv_scales_out)
+    _ctx_env(max_seq_len, sliding_window)
     _serve(
         "native",
         model_name=model,

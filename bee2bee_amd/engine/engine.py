@@ -274,11 +274,18 @@ class InferenceEngine:
         spec_ngram: int = 2,
         kv_dtype: str = "native",
         kv_scales: Optional[str] = None,
+        sliding_window: Optional[int] = None,
     ) -> None:
         """kv_scales (fp8 KV only): None keeps unit scales; a path loads a
         scales file written by save_kv_scales(); "checkpoint" uses the
         self_attn.k_scale / v_scale tensors of the HF checkpoint. Run
-        calibrate_kv_scales() to measure them instead."""
+        calibrate_kv_scales() to measure them instead.
+
+        sliding_window: None takes the model spec's value, 0 forces the
+        window off. The effective window (self.sliding_window) is 0
+        whenever it is >= max_seq_len: no servable context reaches it."""
+        if sliding_window is not None and sliding_window < 0:
+            raise ValueError("sliding_window must be >= 0 (0 = off)")
         if kv_scales is not None and kv_dtype != "fp8":
             raise ValueError(
                 "kv_scales given but the KV cache is not fp8: per-head KV "
@@ -314,6 +321,16 @@ class InferenceEngine:
                 "max_seq_len %d exceeds the decode kernel's %d-token context"
                 " limit; clamping", self.max_seq_len, DECODE_MAX_CTX)
             self.max_seq_len = DECODE_MAX_CTX
+        # effective sliding window: a query at position i attends keys
+        # (i - w, i]. Off (0) when it covers every servable context, so
+        # those engines launch the same kernels and keep the same pages
+        # as a windowless one
+        win = (self.spec.sliding_window if sliding_window is None
+               else sliding_window) or 0
+        self.sliding_window = int(win) if 0 < win < self.max_seq_len else 0
+        # set when release_below() handed pages back: the decode state's
+        # block table is rebuilt on the next step
+        self._window_released = False
         self.tokenizer = load_tokenizer(
             model_path, self.spec.vocab_size, self.spec.bos_token_id, self.spec.eos_token_id
         )
@@ -325,11 +342,14 @@ class InferenceEngine:
             ops.require_hip()
 
         logger.info(
-            "building %s (%.2fB params) on %s dtype=%s",
+            "building %s (%.2fB params) on %s dtype=%s max_seq_len=%d "
+            "sliding_window=%d",
             self.spec.name,
             self.spec.n_params() / 1e9,
             self.device,
             dtype,
+            self.max_seq_len,
+            self.sliding_window,
         )
         self.weights = ModelWeights(self.spec, self.device, dtype)
         if model_path:
@@ -348,7 +368,8 @@ class InferenceEngine:
             raise ValueError("fp8 KV does not support spec_decode yet")
         self.kv = PagedKV(self.spec, self.device, dtype, n_blocks=n_blocks,
                           kv_dtype=kv_dtype)
-        self.runner = Runner(self.spec, self.weights, self.kv, self.device, dtype)
+        self.runner = Runner(self.spec, self.weights, self.kv, self.device,
+                             dtype, window=self.sliding_window)
         if kv_scales == "checkpoint":
             ck = self.weights.kv_scales
             if ck is None:
@@ -695,6 +716,16 @@ class InferenceEngine:
             return True
         return worked
 
+    def _release_window(self, a: "_Active") -> None:
+        """Hand back the pages of `a` that lie wholly below the attention
+        window of every query still to come: the next one sits at position
+        a.length (committed length), so keys < a.length + 1 - window are
+        dead. Call only with a.length at a COMMITTED length (after
+        speculative acceptance, never on the speculative extension)."""
+        if self.sliding_window and self.kv.release_below(
+                a.seq_id, a.length + 1 - self.sliding_window):
+            self._window_released = True
+
     def _need_blocks(self, prompt_len: int, max_new: int) -> int:
         need_len = min(prompt_len + max_new, self.max_seq_len)
         return -(-need_len // self.kv.block_size)
@@ -800,6 +831,8 @@ class InferenceEngine:
                 input_ids, positions, slots, cu_seqlens, max_len,
                 block_table=bt, seq_lens=seq_lens, query_lens=query_lens,
             )
+        for a, _, _ in batch:  # the chunk is committed
+            self._release_window(a)
         self._prefilling = [
             a
             for a, start, take in batch
@@ -836,7 +869,10 @@ class InferenceEngine:
         crosses a KV-block boundary (every block_size tokens)."""
         B = len(self._active)
         dev = self.device
-        blocks_changed = False
+        # pages released below the window since the last step: their table
+        # entries now read 0
+        blocks_changed = self._window_released
+        self._window_released = False
         for a in self._active:
             nblk0 = (a.length + self.kv.block_size - 1) // self.kv.block_size
             self.kv.extend_seq(a.seq_id, a.length + 1)
@@ -915,6 +951,7 @@ class InferenceEngine:
 
         for a in self._active:
             a.length += 1
+            self._release_window(a)
         self._sample_and_emit(self._active, logits)
         done = [a for a in self._active if a.req.done_ts is not None]
         for a in done:
@@ -1076,6 +1113,9 @@ class InferenceEngine:
             # keys get overwritten; attention never reads past seq_len)
             a.length += len(emitted)
             self.kv.extend_seq(a.seq_id, a.length)
+            # release from the accepted length only; the roll-back above
+            # never reaches below it
+            self._release_window(a)
             for tok in emitted:
                 if r.done_ts is not None:
                     break
@@ -1116,6 +1156,7 @@ class InferenceEngine:
             ).to(logits.device, non_blocking=True)
             for a in nong:
                 a.length += 1
+                self._release_window(a)
             self._sample_and_emit(nong, logits[rows], update_last=False)
         self.spec_stats["steps"] += 1
         self._dec_seqs = None  # device decode-state caches are stale
@@ -1279,6 +1320,9 @@ class InferenceEngine:
             "device": str(self.device),
             "kv_dtype": self.kv_dtype,
             "kv_scales": self.kv.scales_source,
+            "max_seq_len": self.max_seq_len,
+            # effective sliding window (0 = full causal attention)
+            "sliding_window": self.sliding_window,
             "active_requests": len(self._active),
             "prefilling_requests": len(self._prefilling),
             "queued_requests": self._pending.qsize(),

@@ -6,6 +6,12 @@ blocks are handed to sequences from a free list. Layout
 [n_blocks, n_kv_heads, block_size, head_dim] keeps one (key, head) row
 contiguous (256 B for hd=128 bf16) — the decode kernel reads it as 64 lanes
 x 4 B, a perfectly coalesced wave read.
+
+Sliding-window models (release_below): pages whose keys all lie below the
+attention window go back to the free list while the sequence lives on. The
+block list keeps its logical layout — a released position holds RELEASED
+and block_table() emits 0 there, the same valid page the padding points to;
+windowed attention never dereferences it.
 """
 from __future__ import annotations
 
@@ -21,6 +27,9 @@ from ..models.spec import ModelSpec
 # Allocation granularity coarsens (one page = 256 tokens per sequence),
 # which the 288 GB pool absorbs.
 BLOCK_SIZE = 256
+
+# block-list marker of a page handed back by release_below()
+RELEASED = -1
 
 
 class PagedKV:
@@ -58,6 +67,8 @@ class PagedKV:
         self._free: List[int] = list(range(n_blocks - 1, -1, -1))
         self._seq_blocks: Dict[int, List[int]] = {}
         self._seq_len: Dict[int, int] = {}
+        # leading block-list positions already released (release_below)
+        self._seq_released: Dict[int, int] = {}
         # Per-(local layer, kv head) fp8 scales: value = float(byte) * scale,
         # byte = e4m3(clamp(x * inv_scale, +-448)). Allocated ONCE and only
         # ever updated in place, so a captured decode graph (which holds the
@@ -139,17 +150,43 @@ class PagedKV:
             self.free_seq(seq_id)
         self._seq_blocks[seq_id] = []
         self._seq_len[seq_id] = 0
+        self._seq_released[seq_id] = 0
 
     def free_seq(self, seq_id: int) -> None:
         blocks = self._seq_blocks.pop(seq_id, [])
         self._seq_len.pop(seq_id, None)
-        self._free.extend(reversed(blocks))
+        # released positions already went back to the free list
+        n_rel = self._seq_released.pop(seq_id, 0)
+        self._free.extend(reversed(blocks[n_rel:]))
+
+    def release_below(self, seq_id: int, first_live_key: int) -> int:
+        """Return to the free list every page of the sequence whose keys
+        are all < first_live_key (a page straddling it stays). The logical
+        layout is kept: slot_mapping of live positions, seq_len and
+        seq_n_blocks do not change. Returns the number of pages released
+        by this call."""
+        blocks = self._seq_blocks[seq_id]
+        n_rel = self._seq_released.get(seq_id, 0)
+        upto = min(max(first_live_key, 0) // self.block_size, len(blocks))
+        for i in range(n_rel, upto):
+            self._free.append(blocks[i])
+            blocks[i] = RELEASED
+        if upto > n_rel:
+            self._seq_released[seq_id] = upto
+            return upto - n_rel
+        return 0
 
     def seq_len(self, seq_id: int) -> int:
         return self._seq_len.get(seq_id, 0)
 
     def seq_n_blocks(self, seq_id: int) -> int:
+        """Logical page count (released positions included)."""
         return len(self._seq_blocks.get(seq_id, ()))
+
+    def seq_live_blocks(self, seq_id: int) -> int:
+        """Pages the sequence still holds (logical count minus released)."""
+        return (len(self._seq_blocks.get(seq_id, ()))
+                - self._seq_released.get(seq_id, 0))
 
     def extend_seq(self, seq_id: int, new_len: int) -> None:
         """Grow a sequence to new_len tokens, allocating blocks as needed."""
@@ -171,11 +208,15 @@ class PagedKV:
         ]
 
     def block_table(self, seq_ids: Sequence[int]) -> torch.Tensor:
-        """Padded [B, max_blocks] int32 device tensor."""
+        """Padded [B, max_blocks] int32 device tensor (0 at released
+        positions, like the padding)."""
         tables = [self._seq_blocks[s] for s in seq_ids]
         width = max(1, max(len(t) for t in tables))
         out = torch.zeros(len(tables), width, dtype=torch.int32)
         for i, t in enumerate(tables):
             if t:
                 out[i, : len(t)] = torch.tensor(t, dtype=torch.int32)
+                n_rel = self._seq_released.get(seq_ids[i], 0)
+                if n_rel:
+                    out[i, :n_rel] = 0
         return out.to(self.device, non_blocking=True)

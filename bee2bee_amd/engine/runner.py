@@ -31,6 +31,7 @@ class Runner:
         device: torch.device,
         dtype: torch.dtype = torch.bfloat16,
         layer_range: Optional[Tuple[int, int]] = None,
+        window: Optional[int] = None,
     ) -> None:
         self.spec = spec
         self.weights = weights
@@ -39,6 +40,12 @@ class Runner:
         self.dtype = dtype
         self.layer_lo, self.layer_hi = layer_range or (0, spec.n_layers)
         self.scale = spec.head_dim**-0.5
+        # sliding-window attention: keys (i - window, i] per query, 0 = off.
+        # None takes the spec's value; the engine passes its effective
+        # window (0 when every servable context fits inside it). A python
+        # int, so a captured decode graph bakes it in as a launch constant.
+        self.window = int(
+            (spec.sliding_window or 0) if window is None else window)
         # optional expert parallelism (parallel/ep.py); when set, MoE layers
         # dispatch tokens over RCCL all-to-all to the expert owners
         self.ep = None
@@ -328,10 +335,15 @@ class Runner:
                 sc = self.kv.layer_scales(layer_idx)
                 kw = {} if sc is None else {"k_scale": sc[0],
                                             "v_scale": sc[1]}
+                if self.window:
+                    kw["window"] = self.window
                 return ops.attn_prefill_paged(
                     q, k_cache, v_cache, block_table, seq_lens, cu_seqlens,
                     max_seqlen, self.scale, **kw
                 )
+            if self.window:
+                return ops.attn_prefill(q, k, v, cu_seqlens, max_seqlen,
+                                        self.scale, window=self.window)
             return ops.attn_prefill(q, k, v, cu_seqlens, max_seqlen, self.scale)
 
         hidden = (
@@ -356,12 +368,18 @@ class Runner:
             sc = self.kv.layer_scales(layer_idx)
             kw = {} if sc is None else {"k_scale": sc[0], "v_scale": sc[1]}
             if self.decode_attn_fn is not None:
+                if self.window:
+                    raise ValueError(
+                        "sliding-window attention is not supported with an "
+                        "injected (context-parallel) decode attention")
                 # injected attention (context parallelism: parallel/cp.py
                 # merges per-rank partials over the local KV shard)
                 return self.decode_attn_fn(
                     q, k_cache, v_cache, block_table, seq_lens, self.scale,
                     **kw
                 )
+            if self.window:
+                kw["window"] = self.window
             return ops.attn_decode(
                 q, k_cache, v_cache, block_table, seq_lens, self.scale, **kw
             )

@@ -55,6 +55,7 @@ class ExportableModel(torch.nn.Module):
         self.register_buffer("rope_cos", freqs.cos())
         self.register_buffer("rope_sin", freqs.sin())
         self.qkv_bias = spec.qkv_bias
+        self.window = int(spec.sliding_window or 0)
         for i, lw in enumerate(weights.layers):
             if lw.wqkv_bias is not None:
                 self.register_buffer(f"wqkv_bias_{i}", lw.wqkv_bias.float())
@@ -113,6 +114,12 @@ class ExportableModel(torch.nn.Module):
         mask = torch.triu(
             torch.full((T, T), float("-inf"), device=h.device), diagonal=1
         )
+        if self.window > 0:
+            # sliding window: row i keeps keys (i - window, i]
+            mask = mask + torch.tril(
+                torch.full((T, T), float("-inf"), device=h.device),
+                diagonal=-self.window,
+            )
         group = self.n_heads // self.n_kv
         for i in range(self.n_layers):
             normed = self._norm(h, i)

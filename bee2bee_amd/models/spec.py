@@ -45,6 +45,10 @@ class ModelSpec:
     # {"rope_type": "llama3", "factor", "low_freq_factor",
     #  "high_freq_factor", "original_max_position_embeddings"}
     rope_scaling: Optional[Dict[str, Any]] = None
+    # sliding-window attention (Mistral-7B-v0.1 / Zephyr: 4096): a query at
+    # position i attends keys (i - w, i], the same window at every layer.
+    # None = full causal attention
+    sliding_window: Optional[int] = None
     # vocab specials (byte-tokenizer defaults; overridden by a real tokenizer)
     bos_token_id: int = 1
     eos_token_id: int = 2
@@ -304,7 +308,11 @@ PRESETS: Dict[str, ModelSpec] = {
         head_dim=128,
         rope_theta=10000.0,
         max_seq_len=8192,
+        # Mistral-7B-v0.1 / Zephyr-7B-beta config.json; no effect until the
+        # engine serves contexts longer than the window
+        sliding_window=4096,
     ),
+    # Mixtral-8x7B-v0.1 ships "sliding_window": null -> stays windowless
     "mixtral-8x7b": ModelSpec(
         name="mixtral-8x7b",
         vocab_size=32000,
@@ -423,6 +431,31 @@ def resolve_spec(name: str, model_path: Optional[str] = None) -> ModelSpec:
     return ModelSpec(**{**spec.__dict__, "name": name})
 
 
+def _sliding_window_from_cfg(cfg: Dict[str, Any]) -> Optional[int]:
+    """The uniform sliding window of a HF config, or None. Qwen2-style
+    configs gate it behind use_sliding_window (every Qwen2.5 checkpoint
+    ships sliding_window=131072 with the flag false) and may window only
+    the layers from max_window_layers up, which this engine does not do."""
+    w = cfg.get("sliding_window")
+    if w is None or "use_sliding_window" in cfg and not cfg[
+            "use_sliding_window"]:
+        return None
+    w = int(w)
+    if w <= 0:
+        return None
+    n_layers = cfg.get("num_hidden_layers", 32)
+    if cfg.get("use_sliding_window") and "max_window_layers" in cfg:
+        mwl = int(cfg["max_window_layers"])
+        if mwl < n_layers:
+            raise ValueError(
+                f"config windows only layers >= {mwl} of {n_layers} "
+                "(use_sliding_window with max_window_layers): per-layer "
+                "sliding windows are not supported")
+        if mwl >= n_layers:
+            return None  # no layer is windowed
+    return w
+
+
 def spec_from_hf_config(model_path: str, name: Optional[str] = None) -> ModelSpec:
     """Parse a HuggingFace config.json (Llama/Mistral/Mixtral/GPT-2 keys)."""
     with open(os.path.join(model_path, "config.json")) as f:
@@ -458,6 +491,7 @@ def spec_from_hf_config(model_path: str, name: Optional[str] = None) -> ModelSpe
                 "rope_type", (cfg.get("rope_scaling") or {}).get("type"))
             == "llama3" else None
         ),
+        sliding_window=_sliding_window_from_cfg(cfg),
         n_experts=cfg.get("num_local_experts", 0),
         top_k_experts=cfg.get("num_experts_per_tok", 2),
         # Qwen2 sets attention_bias (or ships q/k/v bias tensors implicitly)

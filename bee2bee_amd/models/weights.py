@@ -548,5 +548,12 @@ def save_hf(weights: ModelWeights, out_dir: str) -> None:
     if s.is_moe:
         cfg["num_local_experts"] = s.n_experts
         cfg["num_experts_per_tok"] = s.top_k_experts
+    if s.sliding_window:
+        cfg["sliding_window"] = int(s.sliding_window)
+        if not s.is_moe and not s.qkv_bias:
+            # the llama config class knows no window: a windowed dense
+            # checkpoint is a Mistral one, and loads as such elsewhere
+            cfg["model_type"] = "mistral"
+            cfg["architectures"] = ["MistralForCausalLM"]
     with open(os.path.join(out_dir, "config.json"), "w") as f:
         json.dump(cfg, f, indent=2)

@@ -140,15 +140,19 @@ def attn_decode(
     scale: float,
     k_scale: Optional[torch.Tensor] = None,
     v_scale: Optional[torch.Tensor] = None,
+    window: int = 0,
 ) -> torch.Tensor:
     """k_scale / v_scale: optional fp32 [n_kv_heads] dequantization scales
-    of a scaled fp8 cache (value = float(byte) * scale[h])."""
+    of a scaled fp8 cache (value = float(byte) * scale[h]). window > 0:
+    sliding-window attention over keys [max(0, L - window), L); 0 = off."""
     if _use_hip(q):
         return require_hip().attn_decode(
-            q, k_cache, v_cache, block_table, seq_lens, scale, k_scale, v_scale
+            q, k_cache, v_cache, block_table, seq_lens, scale, k_scale,
+            v_scale, window
         )
     return reference.attn_decode(q, k_cache, v_cache, block_table, seq_lens,
-                                 scale, k_scale=k_scale, v_scale=v_scale)
+                                 scale, k_scale=k_scale, v_scale=v_scale,
+                                 window=window)
 
 
 def attn_decode_lse(
@@ -160,17 +164,19 @@ def attn_decode_lse(
     scale: float,
     k_scale: Optional[torch.Tensor] = None,
     v_scale: Optional[torch.Tensor] = None,
+    window: int = 0,
 ):
     """attn_decode that ALSO returns the per-(seq, q-head) flash merge
     state (m, l) — what context-parallel ranks exchange (parallel/cp.py)."""
     if _use_hip(q):
         out, ml = require_hip().attn_decode_lse(
-            q, k_cache, v_cache, block_table, seq_lens, scale, k_scale, v_scale
+            q, k_cache, v_cache, block_table, seq_lens, scale, k_scale,
+            v_scale, window
         )
         return out, ml
     return reference.attn_decode_lse(
         q, k_cache, v_cache, block_table, seq_lens, scale,
-        k_scale=k_scale, v_scale=v_scale)
+        k_scale=k_scale, v_scale=v_scale, window=window)
 
 
 def attn_prefill(
@@ -181,12 +187,15 @@ def attn_prefill(
     max_seqlen: int,
     scale: float,
     causal: bool = True,
+    window: int = 0,
 ) -> torch.Tensor:
+    """window > 0 (causal only): row i attends keys (i - window, i]."""
     if _use_hip(q):
         return require_hip().attn_prefill(
-            q, k, v, cu_seqlens, max_seqlen, scale, causal
+            q, k, v, cu_seqlens, max_seqlen, scale, causal, window
         )
-    return reference.attn_prefill(q, k, v, cu_seqlens, max_seqlen, scale, causal)
+    return reference.attn_prefill(q, k, v, cu_seqlens, max_seqlen, scale,
+                                  causal, window=window)
 
 
 def attn_prefill_paged(
@@ -200,18 +209,21 @@ def attn_prefill_paged(
     scale: float,
     k_scale: Optional[torch.Tensor] = None,
     v_scale: Optional[torch.Tensor] = None,
+    window: int = 0,
 ) -> torch.Tensor:
     """Chunked prefill: packed query chunks (cu_q) attend to the full paged
-    history (seq_lens includes the chunk; its K/V are already stored)."""
+    history (seq_lens includes the chunk; its K/V are already stored).
+    window > 0: chunk row r at hist + r attends (hist + r - window,
+    hist + r]."""
     if _use_hip(q):
         return require_hip().attn_prefill_paged(
             q, k_cache, v_cache, block_table, seq_lens, cu_q, max_qlen, scale,
-            k_scale, v_scale
+            k_scale, v_scale, window
         )
     query_lens = cu_q[1:] - cu_q[:-1]
     return reference.attn_decode_with_history(
         q, k_cache, v_cache, block_table, seq_lens, query_lens, scale,
-        k_scale=k_scale, v_scale=v_scale
+        k_scale=k_scale, v_scale=v_scale, window=window
     )
 
 

@@ -31,6 +31,16 @@
 // register counts unchanged. The bf16 instantiations compile the scale
 // code away.
 //
+// Sliding window (window > 0, Mistral-family): the query at L-1 attends
+// keys [lo, L), lo = max(0, L - window). Chunk indices stay absolute, so
+// the scratch layout is unchanged; every stage starts its chunk walk at
+// c0 = lo / DEC_CHUNK, and in the one chunk that straddles lo a key below
+// it is handled exactly like a key >= L: no block-table lookup (the entry
+// may point at a page already handed back to the pool), dummy K row, score
+// forced to -1e30, p = 0, V row never loaded. WINDOWED is a template flag
+// for the reason SCALED is: with it false, lo and c0 fold to 0 and the
+// window-off instantiations are the code they were before.
+//
 // Replaces: the reference's decode path inside transformers.generate()
 // (bee2bee/hf.py:84-108). Numerics reference: ops/reference.py attn_decode.
 #include "common.h"
@@ -159,7 +169,7 @@ __device__ __forceinline__ void score_row(const KVT* kr,
     }
 }
 
-template <int G, typename KVT>
+template <int G, typename KVT, bool WINDOWED>
 __global__ __launch_bounds__(DEC_BLOCK) void attn_scores_kernel(
     const unsigned short* __restrict__ q,        // [B, nq, hd] (strided)
     const KVT* __restrict__ k_cache,             // [nb, nkv, bs, hd]
@@ -168,11 +178,14 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_scores_kernel(
     unsigned short* __restrict__ p_out,          // [B, nkv, C, CHUNK, G] bf16
     float* __restrict__ part_ml,                 // [B, nkv, C, G, 2]
     int nkv, int W, int bs, int hd, int C, long q_stride, float scale,
-    const float* __restrict__ k_scale) {         // [nkv] or nullptr
+    const float* __restrict__ k_scale,           // [nkv] or nullptr
+    int window) {                                // read iff WINDOWED
     const int b = blockIdx.x;
     const int kvh = blockIdx.y;
     const int L = seq_lens[b];
-    if ((int)blockIdx.z * DEC_CHUNK >= L) return;
+    const int lo = WINDOWED ? max(0, L - window) : 0;  // first live key
+    const int c0 = WINDOWED ? lo / DEC_CHUNK : 0;      // first live chunk
+    if ((c0 + (int)blockIdx.z) * DEC_CHUNK >= L) return;
     const int lane = threadIdx.x % WAVE;
     const int wid = threadIdx.x / WAVE;
     const bool scaled = sizeof(KVT) == 1 && k_scale != nullptr;
@@ -195,10 +208,12 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_scores_kernel(
     // ALL chunks of (b, kvh), so every chunk's p/(m,l) must be produced even
     // when the launcher picks Z < ceil(L/DEC_CHUNK) (a single-
     // chunk kernel left chunks >= Z uninitialized for hd not in {64,128})
-    for (int chunk = blockIdx.z; chunk * DEC_CHUNK < L; chunk += gridDim.z) {
+    for (int chunk = c0 + blockIdx.z; chunk * DEC_CHUNK < L;
+         chunk += gridDim.z) {
     const int start = chunk * DEC_CHUNK;
     const int key = start + threadIdx.x;  // one key per thread
-    const bool valid = key < L;
+    // a key below the window is treated exactly like a key past L
+    const bool valid = key < L && (!WINDOWED || key >= lo);
 
     float s[G];
 #pragma unroll
@@ -298,7 +313,7 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_scores_kernel(
 //   A (16x32): lane = row (l&15), k = (l>>4)*8+e
 //   B (32x16): lane = col (l&15), k = (l>>4)*8+e
 //   C (16x16): lane = col (l&15), row = (l>>4)*4+r
-template <int G, int HD, typename KVT, bool SCALED>
+template <int G, int HD, typename KVT, bool SCALED, bool WINDOWED>
 __global__ __launch_bounds__(DEC_BLOCK) void attn_scores_mfma_kernel(
     const unsigned short* __restrict__ q,
     const KVT* __restrict__ k_cache,
@@ -307,13 +322,16 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_scores_mfma_kernel(
     unsigned short* __restrict__ p_out,  // bf16
     float* __restrict__ part_ml,
     int nkv, int W, int bs, int C, long q_stride, float scale,
-    const float* __restrict__ k_scale) {  // [nkv]; read iff SCALED
+    const float* __restrict__ k_scale,    // [nkv]; read iff SCALED
+    int window) {                         // read iff WINDOWED
     constexpr int KSTEPS = HD / 32;
     constexpr int TILES = WAVE / 16;  // 4 key-tiles of 16 per wave
     const int b = blockIdx.x;
     const int kvh = blockIdx.y;
     const int L = seq_lens[b];
-    if ((int)blockIdx.z * DEC_CHUNK >= L) return;
+    const int lo = WINDOWED ? max(0, L - window) : 0;  // first live key
+    const int c0 = WINDOWED ? lo / DEC_CHUNK : 0;      // first live chunk
+    if ((c0 + (int)blockIdx.z) * DEC_CHUNK >= L) return;
     float ksc = 1.f;
     if (SCALED) ksc = k_scale[kvh];  // uniform: one scalar load
     const int lane = threadIdx.x % WAVE;
@@ -386,7 +404,8 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_scores_mfma_kernel(
     // loop chunks with stride gridDim.z: the q staging amortizes and the
     // per-chunk softmax tail overlaps other chunks' K bursts (single-chunk
     // blocks measured ~66% memory-idle from cold-start/tail phases)
-    for (int chunk = blockIdx.z; chunk * DEC_CHUNK < L; chunk += gridDim.z) {
+    for (int chunk = c0 + blockIdx.z; chunk * DEC_CHUNK < L;
+         chunk += gridDim.z) {
     const int start = chunk * DEC_CHUNK;
     const int wave_key0 = start + wid * WAVE;  // this wave covers 64 keys
 
@@ -398,11 +417,13 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_scores_mfma_kernel(
     for (int t = 0; t < TILES; ++t) {
         const int key = wave_key0 + t * 16 + li;  // A row = li
         const KVT* kr;
-        if (key < L) {
+        if (key < L && (!WINDOWED || key >= lo)) {
             const int page = bt[key / bs];
             kr = k_cache + (((long)page * nkv + kvh) * bs + key % bs) * HD;
         } else {
-            // safe dummy row; masked later via the key<L score mask
+            // safe dummy row; masked later via the key<L score mask (a
+            // key below the window takes the same route: its block-table
+            // entry may be stale, so it is never looked up)
             kr = k_cache;
         }
 #pragma unroll
@@ -427,8 +448,9 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_scores_mfma_kernel(
         for (int r = 0; r < 4; ++r) {
             const int key = wave_key0 + t * 16 + lg * 4 + r;
             // SCALED: per-head K dequant scale on the fp32 score
-            float v = (key < L) ? (SCALED ? acc[t][r] * ksc : acc[t][r])
-                                : -1e30f;
+            const bool live = key < L && (!WINDOWED || key >= lo);
+            float v = live ? (SCALED ? acc[t][r] * ksc : acc[t][r])
+                           : -1e30f;
             sv[t * 4 + r] = v;
             lmax = fmaxf(lmax, v);
         }
@@ -497,7 +519,7 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_scores_mfma_kernel(
 // sizes where B*nkv >= 4096), the kernel carries the running flash-decoding
 // merge (M, l, acc) across chunks in registers and writes the normalized
 // bf16 output directly: no part_o round-trip, no combine kernel.
-template <int G, bool FOLD, typename KVT>
+template <int G, bool FOLD, typename KVT, bool WINDOWED>
 __global__ __launch_bounds__(DEC_BLOCK) void attn_pv_kernel(
     const KVT* __restrict__ v_cache,             // [nb, nkv, bs, hd]
     const int* __restrict__ block_table,
@@ -512,11 +534,14 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_pv_kernel(
                                                  // state for context
                                                  // parallelism (parallel/cp)
     int nkv, int W, int bs, int hd, int C,
-    const float* __restrict__ v_scale) {         // [nkv] or nullptr
+    const float* __restrict__ v_scale,           // [nkv] or nullptr
+    int window) {                                // read iff WINDOWED
     const int b = blockIdx.x;
     const int kvh = blockIdx.y;
     const int L = seq_lens[b];
-    if ((int)blockIdx.z * DEC_CHUNK >= L) return;
+    const int lo = WINDOWED ? max(0, L - window) : 0;  // first live key
+    const int c0 = WINDOWED ? lo / DEC_CHUNK : 0;      // first live chunk
+    if ((c0 + (int)blockIdx.z) * DEC_CHUNK >= L) return;
     const int lane = threadIdx.x % WAVE;
     const int wid = threadIdx.x / WAVE;
     const bool scaled = sizeof(KVT) == 1 && v_scale != nullptr;
@@ -544,7 +569,8 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_pv_kernel(
         }
     }
 
-    for (int chunk = blockIdx.z; chunk * DEC_CHUNK < L; chunk += gridDim.z) {
+    for (int chunk = c0 + blockIdx.z; chunk * DEC_CHUNK < L;
+         chunk += gridDim.z) {
     const int start = chunk * DEC_CHUNK;
     // stage p for the whole chunk into LDS, widening bf16 -> fp32 so the
     // inner fma loop reads full-rate f32x4
@@ -563,7 +589,7 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_pv_kernel(
         const int* bt = block_table + (long)b * W;
         const int key = start + threadIdx.x;
         long voff = 0;
-        if (key < L) {
+        if (key < L && (!WINDOWED || key >= lo)) {
             const int page = bt[key / bs];
             voff = (((long)page * nkv + kvh) * bs + key % bs) * hd;
         }
@@ -571,18 +597,22 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_pv_kernel(
     }
     __syncthreads();
 
-    // wave wid accumulates keys [wid*64, wid*64+64) of the chunk;
-    // lane owns output dims (d0, d0+1)
+    // wave wid accumulates the live keys [kfirst, nkeys) of its slice
+    // [wid*64, wid*64+64) of the chunk (kfirst > 0 only where the window's
+    // lower edge falls inside the slice: V rows below it are never
+    // loaded); lane owns output dims (d0, d0+1)
     const int d0 = lane * 2;
     const int wave_start = wid * WAVE;
     const int nkeys = min(WAVE, L - (start + wave_start));
+    const int kfirst =
+        WINDOWED ? min(WAVE, max(0, lo - (start + wave_start))) : 0;
     float o0[G], o1[G];
 #pragma unroll
     for (int g = 0; g < G; ++g) o0[g] = o1[g] = 0.f;
-    if (d0 < hd && nkeys > 0) {
+    if (d0 < hd && nkeys > kfirst) {
         const long* voffs = voff_s + wave_start;
         const float* pw = p_s + wave_start * G;
-        int t = 0;
+        int t = kfirst;
         for (; t + 32 <= nkeys; t += 32) {  // 32 V loads in flight
             kv_pair_t<KVT> vv[32];
 #pragma unroll
@@ -834,33 +864,36 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_pv_mfma_kernel(
 }
 
 // ------------------------------------------------------ stage 3: combine
-template <int G>
+template <int G, bool WINDOWED>
 __global__ __launch_bounds__(DEC_BLOCK) void attn_decode_combine_kernel(
     const float* __restrict__ part_o,   // [B, nkv, C, G, hd]
     const float* __restrict__ part_ml,  // [B, nkv, C, G, 2]
     const int* __restrict__ seq_lens,
     unsigned short* __restrict__ out,   // [B, nq, hd]
     float* __restrict__ out_ml,         // optional [B, nq, 2] (see PV)
-    int nkv, int hd, int C) {
+    int nkv, int hd, int C,
+    int window) {                       // read iff WINDOWED
     const int b = blockIdx.x;
     const int kvh = blockIdx.y;
     const int g = blockIdx.z;  // one block per (seq, kv head, q head)
     const int nq = nkv * G;
     const int L = seq_lens[b];
     const int nc = (L + DEC_CHUNK - 1) / DEC_CHUNK;
+    // chunks wholly below the window were never produced: walk c0..nc
+    const int c0 = WINDOWED ? max(0, L - window) / DEC_CHUNK : 0;
     const long base = ((long)b * nkv + kvh) * C;
 
     // stage this head's (m, l) pairs once
     __shared__ float ml_s[128][2];  // C <= 128 (32768-token contexts)
-    for (int c = threadIdx.x; c < nc; c += DEC_BLOCK) {
+    for (int c = c0 + threadIdx.x; c < nc; c += DEC_BLOCK) {
         ml_s[c][0] = part_ml[((base + c) * G + g) * 2];
         ml_s[c][1] = part_ml[((base + c) * G + g) * 2 + 1];
     }
     __syncthreads();
     float M = -1e30f;
-    for (int c = 0; c < nc; ++c) M = fmaxf(M, ml_s[c][0]);
+    for (int c = c0; c < nc; ++c) M = fmaxf(M, ml_s[c][0]);
     float Ltot = 0.f;
-    for (int c = 0; c < nc; ++c) Ltot += __expf(ml_s[c][0] - M) * ml_s[c][1];
+    for (int c = c0; c < nc; ++c) Ltot += __expf(ml_s[c][0] - M) * ml_s[c][1];
     const float inv = (Ltot > 0.f) ? 1.f / Ltot : 0.f;
     if (out_ml != nullptr && threadIdx.x == 0) {
         float* mlrow = out_ml + ((long)b * nq + kvh * G + g) * 2;
@@ -870,7 +903,7 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_decode_combine_kernel(
 
     for (int d = threadIdx.x; d < hd; d += DEC_BLOCK) {
         float acc = 0.f;
-        for (int c = 0; c < nc; ++c)
+        for (int c = c0; c < nc; ++c)
             acc += __expf(ml_s[c][0] - M) *
                    part_o[((base + c) * G + g) * hd + d];
         out[((long)b * nq + kvh * G + g) * hd + d] = f2bf(acc * inv);
@@ -878,34 +911,38 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_decode_combine_kernel(
 }
 
 // MFMA scores launch: SCALED only exists for the fp8 cache type
-template <int G, int HD, typename KVT>
+template <int G, int HD, typename KVT, bool WIN>
 static void launch_scores_mfma(
     dim3 grid, int smem, hipStream_t stream, const unsigned short* q,
     const KVT* kc, const int* block_table, const int* seq_lens,
     unsigned short* p_buf, float* part_ml, int nkv, int W, int bs, int C,
-    long q_stride, float scale, const float* k_scale) {
+    long q_stride, float scale, const float* k_scale, int window) {
     if constexpr (sizeof(KVT) == 1) {
         if (k_scale != nullptr) {
-            hipLaunchKernelGGL((attn_scores_mfma_kernel<G, HD, KVT, true>),
-                               grid, dim3(DEC_BLOCK), smem, stream, q, kc,
-                               block_table, seq_lens, p_buf, part_ml, nkv, W,
-                               bs, C, q_stride, scale, k_scale);
+            hipLaunchKernelGGL(
+                (attn_scores_mfma_kernel<G, HD, KVT, true, WIN>), grid,
+                dim3(DEC_BLOCK), smem, stream, q, kc, block_table, seq_lens,
+                p_buf, part_ml, nkv, W, bs, C, q_stride, scale, k_scale,
+                window);
             return;
         }
     }
-    hipLaunchKernelGGL((attn_scores_mfma_kernel<G, HD, KVT, false>), grid,
-                       dim3(DEC_BLOCK), smem, stream, q, kc, block_table,
-                       seq_lens, p_buf, part_ml, nkv, W, bs, C, q_stride,
-                       scale, nullptr);
+    hipLaunchKernelGGL((attn_scores_mfma_kernel<G, HD, KVT, false, WIN>),
+                       grid, dim3(DEC_BLOCK), smem, stream, q, kc,
+                       block_table, seq_lens, p_buf, part_ml, nkv, W, bs, C,
+                       q_stride, scale, nullptr, window);
 }
 
+// window > 0: sliding-window attention, keys [max(0, L - window), L) are
+// live. It selects the WINDOWED instantiations; window == 0 launches the
+// same code as before the window existed (the flag folds lo and c0 to 0).
 extern "C" void launch_attn_decode(
     const unsigned short* q, const void* k_cache, const void* v_cache,
     const int* block_table, const int* seq_lens, unsigned short* p_buf,
     float* part_o, float* part_ml, unsigned short* out, float* out_ml,
     int B, int nkv,
     int G, int W, int bs, int hd, int C, long q_stride, float scale,
-    int fp8, const float* k_scale, const float* v_scale,
+    int fp8, const float* k_scale, const float* v_scale, int window,
     hipStream_t stream) {
     // enough blocks to fill the chip, but chunks loop within a block so the
     // cold-start/tail phases amortize over multiple 64 KB K/V bursts
@@ -923,61 +960,66 @@ extern "C" void launch_attn_decode(
     // MFMA PV (attn_pv_mfma_kernel) measured 4.2 TB/s vs the VALU PV's
     // 4.5 at B768/G4: the barrier-paced LDS pipeline loses more latency
     // hiding than the matrix pipe saves (PV is latency-, not VALU-bound).
-    // Kept as opt-in infrastructure for future tr_b16 staging work.
+    // Kept as opt-in infrastructure for future tr_b16 staging work. It
+    // knows no window: a windowed launch takes the VALU PV path.
     static int pv_mfma = -1;
     if (pv_mfma < 0) {
         const char* e = getenv("BEE2BEE_PV_MFMA");
         pv_mfma = (e != nullptr && e[0] == '1') ? 1 : 0;
     }
-#define LAUNCH_T(GG, KVT)                                                      \
+#define LAUNCH_T(GG, KVT, WIN)                                                 \
     do {                                                                       \
         const KVT* kc = reinterpret_cast<const KVT*>(k_cache);                 \
         const KVT* vc = reinterpret_cast<const KVT*>(v_cache);                 \
         if (hd == 128)                                                         \
-            launch_scores_mfma<GG, 128, KVT>(grid, smem_s, stream, q, kc,      \
-                                             block_table, seq_lens, p_buf,     \
-                                             part_ml, nkv, W, bs, C, q_stride, \
-                                             scale, k_scale);                  \
+            launch_scores_mfma<GG, 128, KVT, WIN>(                             \
+                grid, smem_s, stream, q, kc, block_table, seq_lens, p_buf,     \
+                part_ml, nkv, W, bs, C, q_stride, scale, k_scale, window);     \
         else if (hd == 64)                                                     \
-            launch_scores_mfma<GG, 64, KVT>(grid, smem_s, stream, q, kc,       \
-                                            block_table, seq_lens, p_buf,      \
-                                            part_ml, nkv, W, bs, C, q_stride,  \
-                                            scale, k_scale);                   \
+            launch_scores_mfma<GG, 64, KVT, WIN>(                              \
+                grid, smem_s, stream, q, kc, block_table, seq_lens, p_buf,     \
+                part_ml, nkv, W, bs, C, q_stride, scale, k_scale, window);     \
         else                                                                   \
-            hipLaunchKernelGGL((attn_scores_kernel<GG, KVT>), grid,            \
+            hipLaunchKernelGGL((attn_scores_kernel<GG, KVT, WIN>), grid,       \
                                dim3(DEC_BLOCK), smem_s, stream, q, kc,         \
                                block_table, seq_lens, p_buf, part_ml, nkv, W,  \
-                               bs, hd, C, q_stride, scale, k_scale);           \
-        if (hd == 128 && pv_mfma && !fp8) {                                    \
+                               bs, hd, C, q_stride, scale, k_scale, window);   \
+        if (!WIN && hd == 128 && pv_mfma && !fp8) {                            \
             hipLaunchKernelGGL(attn_pv_mfma_kernel<GG>, grid,                  \
                                dim3(DEC_BLOCK), smem_pvm, stream,              \
                                reinterpret_cast<const unsigned short*>(        \
                                    v_cache),                                   \
                                block_table, seq_lens, p_buf, part_o, nkv, W,   \
                                bs, C);                                         \
-            hipLaunchKernelGGL(attn_decode_combine_kernel<GG>, cgrid,          \
+            hipLaunchKernelGGL((attn_decode_combine_kernel<GG, false>), cgrid, \
                                dim3(DEC_BLOCK), 0, stream, part_o, part_ml,    \
-                               seq_lens, out, out_ml, nkv, hd, C);             \
+                               seq_lens, out, out_ml, nkv, hd, C, 0);          \
         } else if (Z == 1) {                                                   \
-            hipLaunchKernelGGL((attn_pv_kernel<GG, true, KVT>), grid,          \
+            hipLaunchKernelGGL((attn_pv_kernel<GG, true, KVT, WIN>), grid,     \
                                dim3(DEC_BLOCK), smem_pv, stream, vc,           \
                                block_table, seq_lens, p_buf, part_o, part_ml,  \
-                               out, out_ml, nkv, W, bs, hd, C, v_scale);       \
+                               out, out_ml, nkv, W, bs, hd, C, v_scale,        \
+                               window);                                        \
         } else {                                                               \
-            hipLaunchKernelGGL((attn_pv_kernel<GG, false, KVT>), grid,         \
+            hipLaunchKernelGGL((attn_pv_kernel<GG, false, KVT, WIN>), grid,    \
                                dim3(DEC_BLOCK), smem_pv, stream, vc,           \
                                block_table, seq_lens, p_buf, part_o,           \
                                part_ml, out, nullptr, nkv, W, bs, hd, C,       \
-                               v_scale);                                       \
-            hipLaunchKernelGGL(attn_decode_combine_kernel<GG>, cgrid,          \
+                               v_scale, window);                               \
+            hipLaunchKernelGGL((attn_decode_combine_kernel<GG, WIN>), cgrid,   \
                                dim3(DEC_BLOCK), 0, stream, part_o, part_ml,    \
-                               seq_lens, out, out_ml, nkv, hd, C);             \
+                               seq_lens, out, out_ml, nkv, hd, C, window);     \
         }                                                                      \
     } while (0)
 #define LAUNCH(GG)                                                             \
     do {                                                                       \
-        if (fp8) LAUNCH_T(GG, unsigned char);                                  \
-        else LAUNCH_T(GG, unsigned short);                                     \
+        if (window > 0) {                                                      \
+            if (fp8) LAUNCH_T(GG, unsigned char, true);                        \
+            else LAUNCH_T(GG, unsigned short, true);                           \
+        } else {                                                               \
+            if (fp8) LAUNCH_T(GG, unsigned char, false);                       \
+            else LAUNCH_T(GG, unsigned short, false);                          \
+        }                                                                      \
     } while (0)
     switch (G) {
         case 1: LAUNCH(1); break;

@@ -25,6 +25,17 @@
 // dequant-to-LDS time. Both are scalar loads (kvh is block-uniform); the
 // bf16 instantiations compile the scale code away.
 //
+// Sliding window (window > 0, causal only): query row r at absolute
+// position hist + r attends keys (hist + r - window, hist + r]. The key
+// loop of a q tile starts at the PF_TN-aligned lower bound of the tile's
+// FIRST row, staging loads are predicated on that row's exact bound (a
+// paged entry below it may point at a page already handed back to the
+// pool; the staged K/V there are zero), and the mask adds the per-row
+// lower edge. Later rows of the tile see whole key tiles masked before
+// their first live key: the "sfrag <= -1e29 -> p = 0" guard is what keeps
+// m_run = -1e30 from turning exp(s - m) into exp(0) there. WINDOWED is a
+// template flag so the window-off instantiations are unchanged code.
+//
 // Numerics reference: ops/reference.py attn_prefill.
 #include "common.h"
 
@@ -48,7 +59,7 @@ __device__ __forceinline__ bf16x8 load_kv8_bf16(const unsigned char* p) {
 }
 
 // ------------------------------------------------------------------ basic
-template <bool PAGED, typename KVT>
+template <bool PAGED, typename KVT, bool WINDOWED>
 __global__ __launch_bounds__(64) void attn_prefill_basic(
     const unsigned short* __restrict__ q,  // [T, nq, hd]
     const KVT* __restrict__ k,  // [T,nkv,hd] | PAGED: [nb,nkv,bs,hd]
@@ -60,7 +71,8 @@ __global__ __launch_bounds__(64) void attn_prefill_basic(
     int nq, int nkv, int hd, long s_q, long s_k, long s_v, int W, int bs,
     float scale, int causal,
     const float* __restrict__ k_scale,     // [nkv] or nullptr (fp8 only)
-    const float* __restrict__ v_scale) {
+    const float* __restrict__ v_scale,
+    int window) {                          // read iff WINDOWED (causal)
     const int seq = blockIdx.y;
     const int h = blockIdx.x;
     const int kvh = h / (nq / nkv);
@@ -87,7 +99,9 @@ __global__ __launch_bounds__(64) void attn_prefill_basic(
         const int kmax = causal ? hist + r + 1 : L;
         float m = -1e30f, lsum = 0.f, o0 = 0.f, o1 = 0.f;
         const int d0 = lane * 2;
-        for (int base = 0; base < kmax; base += WAVE) {
+        // first live key of this row; every key in [kmin, kmax) is live
+        const int kmin = WINDOWED ? max(0, hist + r - window + 1) : 0;
+        for (int base = kmin; base < kmax; base += WAVE) {
             const int key = base + lane;
             float s = -1e30f;
             if (key < kmax) {
@@ -147,7 +161,7 @@ __global__ __launch_bounds__(64) void attn_prefill_basic(
 #define PF_TN 64                     // kv tile (4 x 16-key fragments)
 #define PF_PAD 8                     // LDS row padding (bf16 elems)
 
-template <int HD, bool PAGED, typename KVT>
+template <int HD, bool PAGED, typename KVT, bool WINDOWED>
 __global__ __launch_bounds__(256) void attn_prefill_mfma(
     const unsigned short* __restrict__ q,
     const KVT* __restrict__ k,  // PAGED: k_cache [nb,nkv,bs,hd]
@@ -159,7 +173,8 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma(
     int nq, int nkv, long s_q, long s_k, long s_v, int W, int bs,
     float scale,
     const float* __restrict__ k_scale,     // [nkv] or nullptr (fp8 only)
-    const float* __restrict__ v_scale) {
+    const float* __restrict__ v_scale,
+    int window) {                          // read iff WINDOWED
     constexpr int KSTEPS = HD / 32;
     const int seq = blockIdx.z;
     const int h = blockIdx.y;
@@ -228,8 +243,12 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma(
 
     // causal: keys up to the last absolute q position of this tile
     const int kv_end = min(L, hist + q0 + PF_TM);
+    // window: first live key of the tile's first row, and the key tile
+    // that holds it
+    const int kv_lo = WINDOWED ? max(0, hist + q0 - window + 1) : 0;
+    const int kb0 = WINDOWED ? kv_lo / PF_TN * PF_TN : 0;
 
-    for (int kb = 0; kb < kv_end; kb += PF_TN) {
+    for (int kb = kb0; kb < kv_end; kb += PF_TN) {
         // ---- stage K tile [32][HD] and V^T tile [HD][32]
         __syncthreads();
         {
@@ -240,7 +259,7 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma(
                 const int d = (i % THREADS_PER_ROW) * 8;
                 const int gk = kb + key;
                 bf16x8 kraw{}, vraw{};
-                if (gk < kv_end) {
+                if (gk < kv_end && (!WINDOWED || gk >= kv_lo)) {
                     if (PAGED) {
                         const long koff = (((long)bt[gk / bs] * nkv + kvh) *
                                            bs + gk % bs) * HD + d;
@@ -288,7 +307,8 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma(
             for (int r = 0; r < 4; ++r) {
                 const int qrow = q0 + wid * PF_QROWS + lg * 4 + r;
                 const int key = kb + f * 16 + li;
-                if (key > hist + qrow || qrow >= QL || key >= kv_end)
+                if (key > hist + qrow || qrow >= QL || key >= kv_end ||
+                    (WINDOWED && key <= hist + qrow - window))
                     sfrag[f][r] = -1e30f;
                 pmax[r] = fmaxf(pmax[r], sfrag[f][r]);
             }
@@ -381,33 +401,44 @@ static int prefill_mfma_smem(int hd) {
     return (k_bytes > p_bytes ? k_bytes : p_bytes) + vt_bytes;
 }
 
+// window > 0 (causal only; the binding rejects it otherwise) selects the
+// WINDOWED instantiations; 0 launches the same code as before.
 extern "C" void launch_attn_prefill(
     const unsigned short* q, const unsigned short* k, const unsigned short* v,
     const int* cu, unsigned short* out, int nseq, int nq, int nkv, int hd,
     long s_q, long s_k, long s_v, int max_seqlen, float scale, int causal,
-    hipStream_t stream) {
-    if ((hd == 64 || hd == 128) && causal) {
-        const int tiles = (max_seqlen + PF_TM - 1) / PF_TM;
-        dim3 grid(tiles, nq, nseq);
-        const int smem = prefill_mfma_smem(hd);
-        if (hd == 128)
-            hipLaunchKernelGGL((attn_prefill_mfma<128, false, unsigned short>),
-                               grid, dim3(256), smem, stream, q, k, v, cu,
-                               nullptr, nullptr, out, nq, nkv, s_q, s_k, s_v,
-                               0, 0, scale, nullptr, nullptr);
-        else
-            hipLaunchKernelGGL((attn_prefill_mfma<64, false, unsigned short>),
-                               grid, dim3(256), smem, stream, q, k, v, cu,
-                               nullptr, nullptr, out, nq, nkv, s_q, s_k, s_v,
-                               0, 0, scale, nullptr, nullptr);
-        return;
-    }
-    dim3 grid(nq, nseq);
-    const int smem = (hd + WAVE) * 4;
-    hipLaunchKernelGGL((attn_prefill_basic<false, unsigned short>), grid,
-                       dim3(WAVE), smem, stream, q, k, v, cu, nullptr,
-                       nullptr, out, nq, nkv, hd, s_q, s_k, s_v, 0, 0, scale,
-                       causal, nullptr, nullptr);
+    int window, hipStream_t stream) {
+#define PF_LAUNCH(WIN)                                                         \
+    do {                                                                       \
+        if ((hd == 64 || hd == 128) && causal) {                               \
+            const int tiles = (max_seqlen + PF_TM - 1) / PF_TM;                \
+            dim3 grid(tiles, nq, nseq);                                        \
+            const int smem = prefill_mfma_smem(hd);                            \
+            if (hd == 128)                                                     \
+                hipLaunchKernelGGL(                                            \
+                    (attn_prefill_mfma<128, false, unsigned short, WIN>),      \
+                    grid, dim3(256), smem, stream, q, k, v, cu, nullptr,       \
+                    nullptr, out, nq, nkv, s_q, s_k, s_v, 0, 0, scale,         \
+                    nullptr, nullptr, window);                                 \
+            else                                                               \
+                hipLaunchKernelGGL(                                            \
+                    (attn_prefill_mfma<64, false, unsigned short, WIN>),       \
+                    grid, dim3(256), smem, stream, q, k, v, cu, nullptr,       \
+                    nullptr, out, nq, nkv, s_q, s_k, s_v, 0, 0, scale,         \
+                    nullptr, nullptr, window);                                 \
+            return;                                                            \
+        }                                                                      \
+        dim3 grid(nq, nseq);                                                   \
+        const int smem = (hd + WAVE) * 4;                                      \
+        hipLaunchKernelGGL(                                                    \
+            (attn_prefill_basic<false, unsigned short, WIN>), grid,            \
+            dim3(WAVE), smem, stream, q, k, v, cu, nullptr, nullptr, out, nq,  \
+            nkv, hd, s_q, s_k, s_v, 0, 0, scale, causal, nullptr, nullptr,     \
+            window);                                                           \
+    } while (0)
+    if (window > 0) PF_LAUNCH(true);
+    else PF_LAUNCH(false);
+#undef PF_LAUNCH
 }
 
 // Chunked prefill: query chunks (packed varlen, cu) attend to the full
@@ -418,8 +449,8 @@ extern "C" void launch_attn_prefill_paged(
     const int* cu, const int* block_table, const int* seq_lens,
     unsigned short* out, int nseq, int nq, int nkv, int hd, long s_q, int W,
     int bs, int max_qlen, float scale, int fp8, const float* k_scale,
-    const float* v_scale, hipStream_t stream) {
-#define PFP_LAUNCH(KVT)                                                        \
+    const float* v_scale, int window, hipStream_t stream) {
+#define PFP_LAUNCH(KVT, WIN)                                                   \
     do {                                                                       \
         const KVT* kc = reinterpret_cast<const KVT*>(k_cache);                 \
         const KVT* vc = reinterpret_cast<const KVT*>(v_cache);                 \
@@ -428,25 +459,32 @@ extern "C" void launch_attn_prefill_paged(
             dim3 grid(tiles, nq, nseq);                                        \
             const int smem = prefill_mfma_smem(hd);                            \
             if (hd == 128)                                                     \
-                hipLaunchKernelGGL((attn_prefill_mfma<128, true, KVT>), grid,  \
-                                   dim3(256), smem, stream, q, kc, vc, cu,     \
-                                   block_table, seq_lens, out, nq, nkv, s_q,   \
-                                   0, 0, W, bs, scale, k_scale, v_scale);      \
+                hipLaunchKernelGGL(                                            \
+                    (attn_prefill_mfma<128, true, KVT, WIN>), grid,            \
+                    dim3(256), smem, stream, q, kc, vc, cu, block_table,       \
+                    seq_lens, out, nq, nkv, s_q, 0, 0, W, bs, scale, k_scale,  \
+                    v_scale, window);                                          \
             else                                                               \
-                hipLaunchKernelGGL((attn_prefill_mfma<64, true, KVT>), grid,   \
-                                   dim3(256), smem, stream, q, kc, vc, cu,     \
-                                   block_table, seq_lens, out, nq, nkv, s_q,   \
-                                   0, 0, W, bs, scale, k_scale, v_scale);      \
+                hipLaunchKernelGGL(                                            \
+                    (attn_prefill_mfma<64, true, KVT, WIN>), grid, dim3(256),  \
+                    smem, stream, q, kc, vc, cu, block_table, seq_lens, out,   \
+                    nq, nkv, s_q, 0, 0, W, bs, scale, k_scale, v_scale,        \
+                    window);                                                   \
             return;                                                            \
         }                                                                      \
         dim3 grid(nq, nseq);                                                   \
         const int smem = (hd + WAVE) * 4;                                      \
-        hipLaunchKernelGGL((attn_prefill_basic<true, KVT>), grid, dim3(WAVE),  \
-                           smem, stream, q, kc, vc, cu, block_table, seq_lens, \
-                           out, nq, nkv, hd, s_q, 0, 0, W, bs, scale, 1,       \
-                           k_scale, v_scale);                                  \
+        hipLaunchKernelGGL((attn_prefill_basic<true, KVT, WIN>), grid,         \
+                           dim3(WAVE), smem, stream, q, kc, vc, cu,            \
+                           block_table, seq_lens, out, nq, nkv, hd, s_q, 0, 0, \
+                           W, bs, scale, 1, k_scale, v_scale, window);         \
     } while (0)
-    if (fp8) PFP_LAUNCH(unsigned char);
-    else PFP_LAUNCH(unsigned short);
+    if (window > 0) {
+        if (fp8) PFP_LAUNCH(unsigned char, true);
+        else PFP_LAUNCH(unsigned short, true);
+    } else {
+        if (fp8) PFP_LAUNCH(unsigned char, false);
+        else PFP_LAUNCH(unsigned short, false);
+    }
 #undef PFP_LAUNCH
 }

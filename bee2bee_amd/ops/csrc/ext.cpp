@@ -7,6 +7,8 @@
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 
+#include <climits>
+
 using torch::Tensor;
 
 extern "C" {
@@ -38,16 +40,16 @@ void launch_attn_decode(const unsigned short*, const void*, const void*,
                         const int*, const int*, unsigned short*, float*,
                         float*, unsigned short*, float*, int, int, int, int,
                         int, int, int, long, float, int, const float*,
-                        const float*, hipStream_t);
+                        const float*, int, hipStream_t);
 void launch_attn_prefill(const unsigned short*, const unsigned short*,
                          const unsigned short*, const int*, unsigned short*,
                          int, int, int, int, long, long, long, int, float,
-                         int, hipStream_t);
+                         int, int, hipStream_t);
 void launch_attn_prefill_paged(const unsigned short*, const void*,
                                const void*, const int*, const int*,
                                const int*, unsigned short*, int, int, int,
                                int, long, int, int, int, float, int,
-                               const float*, const float*, hipStream_t);
+                               const float*, const float*, int, hipStream_t);
 void launch_mfma_probe(const unsigned short*, const unsigned short*, float*,
                        hipStream_t);
 void launch_mfma_probe_fp8(const unsigned char*, const unsigned char*,
@@ -247,8 +249,10 @@ std::vector<Tensor> attn_decode_impl(const Tensor& q, const Tensor& k_cache,
                                      const Tensor& seq_lens, double scale,
                                      const OptTensor& k_scale,
                                      const OptTensor& v_scale,
-                                     bool want_lse) {
+                                     int64_t window, bool want_lse) {
     check_bf16(q, "q");
+    TORCH_CHECK(window >= 0 && window <= INT_MAX,
+                "attn_decode: window must be >= 0 (0 = off)");
     const bool scaled =
         check_kv_scales(k_scale, v_scale, k_cache, "attn_decode");
     const bool fp8 = k_cache.scalar_type() == torch::kUInt8;
@@ -290,7 +294,7 @@ std::vector<Tensor> attn_decode_impl(const Tensor& q, const Tensor& k_cache,
                        q.stride(0), (float)scale, fp8 ? 1 : 0,
                        scaled ? k_scale->data_ptr<float>() : nullptr,
                        scaled ? v_scale->data_ptr<float>() : nullptr,
-                       stream());
+                       (int)window, stream());
     if (want_lse) return {out, out_ml};
     return {out};
 }
@@ -298,9 +302,10 @@ std::vector<Tensor> attn_decode_impl(const Tensor& q, const Tensor& k_cache,
 Tensor attn_decode(const Tensor& q, const Tensor& k_cache,
                    const Tensor& v_cache, const Tensor& block_table,
                    const Tensor& seq_lens, double scale,
-                   const OptTensor& k_scale, const OptTensor& v_scale) {
+                   const OptTensor& k_scale, const OptTensor& v_scale,
+                   int64_t window) {
     return attn_decode_impl(q, k_cache, v_cache, block_table, seq_lens,
-                            scale, k_scale, v_scale, false)[0];
+                            scale, k_scale, v_scale, window, false)[0];
 }
 
 // out + per-(seq, q-head) (m, l): the flash merge state that context
@@ -310,16 +315,21 @@ std::vector<Tensor> attn_decode_lse(const Tensor& q, const Tensor& k_cache,
                                     const Tensor& block_table,
                                     const Tensor& seq_lens, double scale,
                                     const OptTensor& k_scale,
-                                    const OptTensor& v_scale) {
+                                    const OptTensor& v_scale,
+                                    int64_t window) {
     return attn_decode_impl(q, k_cache, v_cache, block_table, seq_lens,
-                            scale, k_scale, v_scale, true);
+                            scale, k_scale, v_scale, window, true);
 }
 
 Tensor attn_prefill(const Tensor& q, const Tensor& k, const Tensor& v,
                     const Tensor& cu_seqlens, long max_seqlen, double scale,
-                    bool causal) {
+                    bool causal, int64_t window) {
     check_bf16(q, "q");
     check_bf16(k, "k");
+    TORCH_CHECK(window >= 0 && window <= INT_MAX,
+                "attn_prefill: window must be >= 0 (0 = off)");
+    TORCH_CHECK(window == 0 || causal,
+                "attn_prefill: a sliding window needs causal attention");
     TORCH_CHECK(cu_seqlens.scalar_type() == torch::kInt32 &&
                 cu_seqlens.is_contiguous());
     const int T = q.size(0), nq = q.size(1), hd = q.size(2);
@@ -334,7 +344,7 @@ Tensor attn_prefill(const Tensor& q, const Tensor& k, const Tensor& v,
                         cu_seqlens.data_ptr<int>(), bf16p_mut(out), nseq, nq,
                         nkv, hd, q.stride(0), k.stride(0), v.stride(0),
                         (int)max_seqlen, (float)scale, causal ? 1 : 0,
-                        stream());
+                        (int)window, stream());
     return out;
 }
 
@@ -343,8 +353,10 @@ Tensor attn_prefill_paged(const Tensor& q, const Tensor& k_cache,
                           const Tensor& seq_lens, const Tensor& cu_q,
                           long max_qlen, double scale,
                           const OptTensor& k_scale,
-                          const OptTensor& v_scale) {
+                          const OptTensor& v_scale, int64_t window) {
     check_bf16(q, "q");
+    TORCH_CHECK(window >= 0 && window <= INT_MAX,
+                "attn_prefill_paged: window must be >= 0 (0 = off)");
     const bool scaled =
         check_kv_scales(k_scale, v_scale, k_cache, "attn_prefill_paged");
     const bool fp8 = k_cache.scalar_type() == torch::kUInt8;
@@ -371,7 +383,7 @@ Tensor attn_prefill_paged(const Tensor& q, const Tensor& k_cache,
                               (float)scale, fp8 ? 1 : 0,
                               scaled ? k_scale->data_ptr<float>() : nullptr,
                               scaled ? v_scale->data_ptr<float>() : nullptr,
-                              stream());
+                              (int)window, stream());
     return out;
 }
 
@@ -461,19 +473,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("attn_decode", &attn_decode, "paged GQA decode attention",
           py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
           py::arg("block_table"), py::arg("seq_lens"), py::arg("scale"),
-          py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
+          py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none(),
+          py::arg("window") = 0);
     m.def("attn_decode_lse", &attn_decode_lse,
           "paged GQA decode attention + per-head (m, l) merge state",
           py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
           py::arg("block_table"), py::arg("seq_lens"), py::arg("scale"),
-          py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
-    m.def("attn_prefill", &attn_prefill, "varlen causal flash prefill");
+          py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none(),
+          py::arg("window") = 0);
+    m.def("attn_prefill", &attn_prefill, "varlen causal flash prefill",
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_seqlens"),
+          py::arg("max_seqlen"), py::arg("scale"), py::arg("causal"),
+          py::arg("window") = 0);
     m.def("attn_prefill_paged", &attn_prefill_paged,
           "chunked prefill vs paged history", py::arg("q"),
           py::arg("k_cache"), py::arg("v_cache"), py::arg("block_table"),
           py::arg("seq_lens"), py::arg("cu_q"), py::arg("max_qlen"),
           py::arg("scale"), py::arg("k_scale") = py::none(),
-          py::arg("v_scale") = py::none());
+          py::arg("v_scale") = py::none(), py::arg("window") = 0);
     m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
     m.def("mfma_probe_fp8", &mfma_probe_fp8,
           "16x16x32 fp8 MFMA layout probe");

@@ -15,6 +15,12 @@ Conventions (shared with the HIP kernels):
   slot_mapping [T] int32     flat slot = block_id * block_size + offset
   cos/sin  [max_len, hd/2]   fp32 RoPE tables (host-precomputed)
 RoPE is llama-style rotate_half: pair (i, i + hd/2).
+
+Sliding window (`window` keyword of the attention ops, 0 = off): a query at
+absolute position i attends keys j with i - window < j <= i, `window` keys
+including itself (transformers' Mistral mask). With a window the paged ops
+never index a block_table entry whose page lies wholly below the band: the
+engine hands such pages back to the pool and their entries go stale.
 """
 from __future__ import annotations
 
@@ -184,6 +190,7 @@ def attn_decode(
     out_ml: torch.Tensor = None,
     k_scale: torch.Tensor = None,
     v_scale: torch.Tensor = None,
+    window: int = 0,
 ) -> torch.Tensor:
     """Paged single-token attention, GQA. q [B, nq, hd] -> out [B, nq, hd].
     When out_ml [B, nq, 2] is given, also writes the flash merge state
@@ -191,10 +198,13 @@ def attn_decode(
     exchange for context parallelism. k_scale / v_scale [n_kv] are the
     per-kv-head dequantization scales of a scaled fp8 cache: the scores
     (and so m, l) are taken on float(byte) * k_scale, the output on
-    float(byte) * v_scale."""
+    float(byte) * v_scale. window > 0: the query sits at L-1 and only keys
+    [max(0, L - window), L) are live; (m, l) are taken over those."""
     B, nq, hd = q.shape
     _nb, n_kv, block_size, _ = k_cache.shape
     _check_scales(k_cache, k_scale, v_scale)
+    if window < 0:
+        raise ValueError("window must be >= 0 (0 = off)")
     group = nq // n_kv
     out = torch.empty_like(q)
     for b in range(B):
@@ -208,11 +218,17 @@ def attn_decode(
                 out_ml[b, :, 1] = 0.0
             continue
         nblk = (L + block_size - 1) // block_size
-        blocks = block_table[b, :nblk].long()
-        keys = _kv_deq(k_cache[blocks])  # [nblk, n_kv, bs, hd]
+        # first live key and the page that holds it (0, 0 without a window)
+        lo = max(0, L - window) if window > 0 else 0
+        b0 = lo // block_size
+        blocks = block_table[b, b0:nblk].long()
+        keys = _kv_deq(k_cache[blocks])  # [nblk - b0, n_kv, bs, hd]
         vals = _kv_deq(v_cache[blocks])
-        keys = keys.permute(1, 0, 2, 3).reshape(n_kv, nblk * block_size, hd)[:, :L]
-        vals = vals.permute(1, 0, 2, 3).reshape(n_kv, nblk * block_size, hd)[:, :L]
+        span = slice(lo - b0 * block_size, L - b0 * block_size)
+        keys = keys.permute(1, 0, 2, 3).reshape(
+            n_kv, (nblk - b0) * block_size, hd)[:, span]
+        vals = vals.permute(1, 0, 2, 3).reshape(
+            n_kv, (nblk - b0) * block_size, hd)[:, span]
         qb = q[b].float().view(n_kv, group, hd)
         scores = torch.einsum("kgd,kld->kgl", qb, keys) * scale
         scores = _head_scale(scores, k_scale)
@@ -235,9 +251,13 @@ def attn_prefill(
     max_seqlen: int,
     scale: float,
     causal: bool = True,
+    window: int = 0,
 ) -> torch.Tensor:
-    """Varlen full-prompt attention, GQA. q [T, nq, hd] -> [T, nq, hd]."""
+    """Varlen full-prompt attention, GQA. q [T, nq, hd] -> [T, nq, hd].
+    window > 0 (causal only): row i attends keys (i - window, i]."""
     T, nq, hd = q.shape
+    if window < 0 or (window > 0 and not causal):
+        raise ValueError("a sliding window needs window > 0 and causal=True")
     n_kv = k.shape[1]
     group = nq // n_kv
     out = torch.empty_like(q)
@@ -253,6 +273,10 @@ def attn_prefill(
                 torch.ones(L, L, dtype=torch.bool, device=q.device), diagonal=1
             )
             scores.masked_fill_(mask, float("-inf"))
+            if window > 0:
+                pos = torch.arange(L, device=q.device)
+                below = pos.view(1, L) <= pos.view(L, 1) - window
+                scores.masked_fill_(below, float("-inf"))
         probs = torch.softmax(scores, dim=-1)
         oi = torch.einsum("kgql,lkd->qkgd", probs, vi)
         out[s:e] = oi.reshape(L, nq, hd).to(q.dtype)
@@ -269,12 +293,17 @@ def attn_decode_with_history(
     scale: float,
     k_scale: torch.Tensor = None,
     v_scale: torch.Tensor = None,
+    window: int = 0,
 ) -> torch.Tensor:
     """Chunked-prefill attention: multiple new query tokens per sequence
     attending to the full paged history (new tokens already stored in cache).
 
     q [T, nq, hd] packed by sequence; seq_lens = total length incl. the new
-    chunk; query_lens = chunk length per sequence."""
+    chunk; query_lens = chunk length per sequence. window > 0: chunk row r
+    sits at hist + r (hist = L - QL) and attends keys (hist + r - window,
+    hist + r]."""
+    if window < 0:
+        raise ValueError("window must be >= 0 (0 = off)")
     T, nq, hd = q.shape
     _nb, n_kv, block_size, _ = k_cache.shape
     group = nq // n_kv
@@ -285,22 +314,31 @@ def attn_decode_with_history(
         QL = int(query_lens[b])
         L = int(seq_lens[b])
         nblk = (L + block_size - 1) // block_size
-        blocks = block_table[b, :nblk].long()
+        # the chunk's first row has the lowest band edge: pages wholly
+        # below it are not indexed (k0 = first key position gathered)
+        lo = max(0, L - QL - window + 1) if window > 0 else 0
+        b0 = lo // block_size
+        k0 = b0 * block_size
+        blocks = block_table[b, b0:nblk].long()
         keys = (
             _kv_deq(k_cache[blocks])
-            .permute(1, 0, 2, 3).reshape(n_kv, nblk * block_size, hd)[:, :L]
+            .permute(1, 0, 2, 3)
+            .reshape(n_kv, (nblk - b0) * block_size, hd)[:, : L - k0]
         )
         vals = (
             _kv_deq(v_cache[blocks])
-            .permute(1, 0, 2, 3).reshape(n_kv, nblk * block_size, hd)[:, :L]
+            .permute(1, 0, 2, 3)
+            .reshape(n_kv, (nblk - b0) * block_size, hd)[:, : L - k0]
         )
         qb = q[t0 : t0 + QL].float().view(QL, n_kv, group, hd)
         scores = torch.einsum("qkgd,kld->kgql", qb, keys) * scale
         scores = _head_scale(scores, k_scale)
         # causal within the chunk: query j (absolute pos L-QL+j) sees keys <= pos
         qpos = torch.arange(L - QL, L, device=q.device).view(1, 1, QL, 1)
-        kpos = torch.arange(L, device=q.device).view(1, 1, 1, L)
+        kpos = torch.arange(k0, L, device=q.device).view(1, 1, 1, L - k0)
         scores.masked_fill_(kpos > qpos, float("-inf"))
+        if window > 0:
+            scores.masked_fill_(kpos <= qpos - window, float("-inf"))
         probs = torch.softmax(scores, dim=-1)
         ob = torch.einsum("kgql,kld->kgqd", probs, vals)
         ob = _head_scale(ob, v_scale).permute(2, 0, 1, 3)
@@ -349,10 +387,12 @@ def attn_decode_lse(
     scale: float,
     k_scale: torch.Tensor = None,
     v_scale: torch.Tensor = None,
+    window: int = 0,
 ):
     """attn_decode + per-head (m, l) merge state (see parallel/cp.py)."""
     out_ml = torch.empty(q.shape[0], q.shape[1], 2, dtype=torch.float32,
                          device=q.device)
     out = attn_decode(q, k_cache, v_cache, block_table, seq_lens, scale,
-                      out_ml=out_ml, k_scale=k_scale, v_scale=v_scale)
+                      out_ml=out_ml, k_scale=k_scale, v_scale=v_scale,
+                      window=window)
     return out, out_ml

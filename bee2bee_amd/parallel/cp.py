@@ -80,12 +80,18 @@ def cp_attn_decode(
     group: Optional[dist.ProcessGroup] = None,
     k_scale: Optional[torch.Tensor] = None,
     v_scale: Optional[torch.Tensor] = None,
+    window: int = 0,
 ) -> torch.Tensor:
     """Decode attention over a context sharded across the group's ranks.
 
     Every rank passes its LOCAL page table / lengths (build with
     shard_pages/local_lens); returns the full-context attention output,
-    identical on all ranks."""
+    identical on all ranks. The shards carry local lengths, so a global
+    sliding window does not map onto them: window > 0 is refused."""
+    if window:
+        raise ValueError(
+            "context parallelism does not support sliding-window attention "
+            f"(window={window})")
     assert dist.is_initialized(), "init the process group first"
     world = dist.get_world_size(group)
     out, ml = ops.attn_decode_lse(
@@ -141,12 +147,20 @@ class CPEngine:
         from ..models.spec import ModelSpec, resolve_spec
         from ..models.weights import ModelWeights
 
+        spec = model if isinstance(model, ModelSpec) else resolve_spec(
+            model, model_path)
+        # pages are sharded with LOCAL lengths: a global attention band
+        # does not map onto them, so a model whose window would take
+        # effect at this context length is refused rather than served wrong
+        win = int(spec.sliding_window or 0)
+        if 0 < win < min(max_seq_len, spec.max_seq_len):
+            raise ValueError(
+                f"{spec.name}: sliding_window={win} is not supported with "
+                "context parallelism")
         assert dist.is_initialized(), "init the process group first"
         self.group = group
         self.rank = dist.get_rank(group)
         self.world = dist.get_world_size(group)
-        spec = model if isinstance(model, ModelSpec) else resolve_spec(
-            model, model_path)
         self.spec = spec
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
@@ -169,7 +183,8 @@ class CPEngine:
         local_pages = pages_total // self.world + 1
         self.kv = PagedKV(spec, self.device, dtype,
                           n_blocks=max_batch * local_pages + 2)
-        self.runner = Runner(spec, self.weights, self.kv, self.device, dtype)
+        self.runner = Runner(spec, self.weights, self.kv, self.device, dtype,
+                             window=0)
         self.runner.decode_attn_fn = self._cp_attn
         # non-greedy sampling must draw IDENTICAL tokens on every rank
         # (same contract and fix as TPEngine)

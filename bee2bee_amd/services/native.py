@@ -57,12 +57,17 @@ class NativeEngineService(BaseService):
                     "BEE2BEE_KV_SCALES is set but the fp8 KV cache is off: "
                     "set BEE2BEE_KV_FP8=1 (--kv-fp8) as well")
             calibrate = kv_scales == "calibrate"
+            # --max-seq-len / --sliding-window (0 forces the window off;
+            # unset takes the checkpoint's / preset's value)
+            msl = os.environ.get("BEE2BEE_MAX_SEQ_LEN")
+            win = os.environ.get("BEE2BEE_SLIDING_WINDOW")
             self.engine = InferenceEngine(
                 self.model_name,
                 device=self.device,
                 model_path=self.model_path,
                 max_batch=self.max_batch,
-                max_seq_len=self.max_seq_len,
+                max_seq_len=int(msl) if msl else self.max_seq_len,
+                sliding_window=int(win) if win else None,
                 # speculative decoding (prompt-lookup + exact verification):
                 # serving opt-in; greedy outputs are provably unchanged
                 spec_decode=os.environ.get("BEE2BEE_SPEC_DECODE") == "1",
@@ -93,6 +98,8 @@ class NativeEngineService(BaseService):
         if self.engine is not None:
             meta["arch"] = self.engine.spec.name
             meta["device"] = str(self.engine.device)
+            meta["max_seq_len"] = self.engine.max_seq_len
+            meta["sliding_window"] = self.engine.sliding_window
         return meta
 
     def _check(self, params: Dict[str, Any]):

@@ -2,7 +2,9 @@
 
 Usage: python scripts/bench_attn.py [--batch 64] [--len 1024] [--iters 50]
 Prints achieved KV-read bandwidth (the kernel is memory-bound; the roofline
-is ~6.3 TB/s achievable HBM on MI355X).
+is ~6.3 TB/s achievable HBM on MI355X). With --window N (sliding-window
+attention) the bandwidth is taken over the bytes the window leaves to read:
+min(L, N) keys per sequence for decode.
 """
 import argparse
 import os
@@ -30,7 +32,11 @@ def main():
     ap.add_argument("--fp8-scaled", action="store_true",
                     help="the --fp8 bench with non-unit per-kv-head scales "
                          "passed (scaled scores / PV kernels)")
+    ap.add_argument("--window", type=int, default=0,
+                    help="sliding-window attention over the last N keys "
+                         "(0 = off), decode and --prefill")
     args = ap.parse_args()
+    wkw = {"window": args.window} if args.window > 0 else {}
     if args.fp8_scaled:
         args.fp8 = True
 
@@ -51,16 +57,21 @@ def main():
         cu = torch.arange(0, T + 1, L, dtype=torch.int32, device=dev)
         scale = hd**-0.5
         for _ in range(3):
-            out = ops.attn_prefill(q, k, v, cu, L, scale, True)
+            out = ops.attn_prefill(q, k, v, cu, L, scale, True, **wkw)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.iters):
-            out = ops.attn_prefill(q, k, v, cu, L, scale, True)
+            out = ops.attn_prefill(q, k, v, cu, L, scale, True, **wkw)
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / args.iters
-        # causal flops: 4 * nq * hd * L^2/2 per seq (QK^T + PV)
-        flops = 4 * nq * hd * L * L / 2 * B
-        print(f"prefill B{B} L{L} nq{nq} hd{hd}: {dt * 1e3:.3f} ms  "
+        # causal flops: 4 * nq * hd per live (q, key) pair (QK^T + PV);
+        # pairs = L^2/2, minus the (L - w)^2/2 a window w < L masks
+        pairs = L * L / 2
+        if 0 < args.window < L:
+            pairs -= (L - args.window) ** 2 / 2
+        flops = 4 * nq * hd * pairs * B
+        wtag = f" w{args.window}" if args.window > 0 else ""
+        print(f"prefill B{B} L{L} nq{nq} hd{hd}{wtag}: {dt * 1e3:.3f} ms  "
               f"{flops / dt / 1e12:.1f} TF/s")
         return
 
@@ -85,6 +96,7 @@ def main():
             "v_scale": torch.linspace(0.5, 2.0, nkv, device=dev),
         }
 
+    kw.update(wkw)
     for _ in range(5):
         out = ops.attn_decode(q, kc, vc, bt, lens, scale, **kw)
     torch.cuda.synchronize()
@@ -93,11 +105,14 @@ def main():
         out = ops.attn_decode(q, kc, vc, bt, lens, scale, **kw)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.iters
-    kv_bytes = B * L * 2 * nkv * hd * (1 if args.fp8 else 2)
+    live = min(L, args.window) if args.window > 0 else L  # keys read
+    kv_bytes = B * live * 2 * nkv * hd * (1 if args.fp8 else 2)
     print(
         f"decode{' fp8' if args.fp8 else ''}"
         f"{'-scaled' if args.fp8_scaled else ''} "
-        f"B{B} L{L} nkv{nkv} G{G} hd{hd}: {dt * 1e6:.1f} us  "
+        f"B{B} L{L} nkv{nkv} G{G} hd{hd}"
+        f"{f' w{args.window}' if args.window > 0 else ''}: "
+        f"{dt * 1e6:.1f} us  "
         f"KV {kv_bytes / 1e6:.0f} MB  {kv_bytes / dt / 1e12:.2f} TB/s"
     )
     _ = out
