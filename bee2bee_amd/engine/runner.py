@@ -122,7 +122,11 @@ class Runner:
         q = q.view(T, s.n_heads, s.head_dim)
         k = k.view(T, s.n_kv_heads, s.head_dim)
         v = v.view(T, s.n_kv_heads, s.head_dim)
-        if s.pos_type == "rope":
+        if s.qk_norm:  # Qwen3: per-head RMSNorm of q and k, fused with RoPE
+            ops.qk_norm_rope_inplace(q, k, positions, self.rope_cos,
+                                     self.rope_sin, lw.q_norm, lw.k_norm,
+                                     s.rms_eps)
+        elif s.pos_type == "rope":
             ops.rope_inplace(q, k, positions, self.rope_cos, self.rope_sin)
         if self.kv_observer is not None:
             self.kv_observer(layer_idx, k, v)

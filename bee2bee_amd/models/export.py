@@ -56,7 +56,11 @@ class ExportableModel(torch.nn.Module):
         self.register_buffer("rope_sin", freqs.sin())
         self.qkv_bias = spec.qkv_bias
         self.window = int(spec.sliding_window or 0)
+        self.qk_norm = spec.qk_norm
         for i, lw in enumerate(weights.layers):
+            if spec.qk_norm:  # Qwen3 per-head QK-norm weights [head_dim]
+                self.register_buffer(f"q_norm_{i}", lw.q_norm.float())
+                self.register_buffer(f"k_norm_{i}", lw.k_norm.float())
             if lw.wqkv_bias is not None:
                 self.register_buffer(f"wqkv_bias_{i}", lw.wqkv_bias.float())
             self.register_buffer(f"attn_norm_{i}", lw.attn_norm.float())
@@ -129,6 +133,9 @@ class ExportableModel(torch.nn.Module):
             q, k, v = qkv.split([self.q_size, self.kv_size, self.kv_size], -1)
             q = q.view(B, T, self.n_heads, self.hd)
             k = k.view(B, T, self.n_kv, self.hd)
+            if self.qk_norm:
+                q = self._rms(q, getattr(self, f"q_norm_{i}"), self.eps)
+                k = self._rms(k, getattr(self, f"k_norm_{i}"), self.eps)
             if not self.gpt2:
                 q = self._rope(q, T)
                 k = self._rope(k, T)

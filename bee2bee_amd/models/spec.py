@@ -49,6 +49,9 @@ class ModelSpec:
     # position i attends keys (i - w, i], the same window at every layer.
     # None = full causal attention
     sliding_window: Optional[int] = None
+    # Qwen3: RMSNorm over head_dim on every q head and every k head before
+    # RoPE (one [head_dim] weight for q, one for k, per layer)
+    qk_norm: bool = False
     # vocab specials (byte-tokenizer defaults; overridden by a real tokenizer)
     bos_token_id: int = 1
     eos_token_id: int = 2
@@ -75,7 +78,7 @@ class ModelSpec:
             mlp = 2 * h * i
         else:
             mlp = 3 * h * i
-        norms = 2 * h
+        norms = 2 * h + (2 * self.head_dim if self.qk_norm else 0)
         per_layer = attn + mlp + norms
         emb = self.vocab_size * h
         head = 0 if self.tie_embeddings else self.vocab_size * h
@@ -88,7 +91,8 @@ class ModelSpec:
         h, i = self.hidden_size, self.intermediate_size
         attn = h * (self.q_size + 2 * self.kv_size) + self.q_size * h
         mlp = self.top_k_experts * 3 * h * i + h * self.n_experts
-        per_layer = attn + mlp + 2 * h
+        per_layer = attn + mlp + 2 * h + (
+            2 * self.head_dim if self.qk_norm else 0)
         emb = self.vocab_size * h
         head = 0 if self.tie_embeddings else self.vocab_size * h
         return emb + self.n_layers * per_layer + head + h
@@ -329,6 +333,48 @@ PRESETS: Dict[str, ModelSpec] = {
     ),
 }
 
+def _qwen3(name: str, **kw: Any) -> ModelSpec:
+    """Qwen3 family: llama-shaped, no QKV bias, per-head QK-norm, and a
+    head_dim of 128 that is decoupled from hidden_size / n_heads."""
+    base: Dict[str, Any] = dict(
+        vocab_size=151936, head_dim=128, rope_theta=1000000.0, rms_eps=1e-6,
+        max_seq_len=32768, qkv_bias=False, qk_norm=True,
+        bos_token_id=151643, eos_token_id=151645,
+    )
+    base.update(kw)
+    return ModelSpec(name=name, **base)
+
+
+# (hidden, intermediate, layers, heads, kv heads, tied embeddings)
+for _name, _dims in {
+    "qwen3-0.6b": (1024, 3072, 28, 16, 8, True),
+    "qwen3-1.7b": (2048, 6144, 28, 16, 8, True),
+    "qwen3-4b": (2560, 9728, 36, 32, 8, True),
+    "qwen3-8b": (4096, 12288, 36, 32, 8, False),
+    "qwen3-14b": (5120, 17408, 40, 40, 8, False),
+    "qwen3-32b": (5120, 25600, 64, 64, 8, False),
+}.items():
+    PRESETS[_name] = _qwen3(
+        _name, hidden_size=_dims[0], intermediate_size=_dims[1],
+        n_layers=_dims[2], n_heads=_dims[3], n_kv_heads=_dims[4],
+        tie_embeddings=_dims[5])
+# Qwen3-30B-A3B: 128 experts, top-8; intermediate_size is the per-expert
+# width (HF moe_intermediate_size)
+PRESETS["qwen3-30b-a3b"] = _qwen3(
+    "qwen3-30b-a3b", hidden_size=2048, intermediate_size=768, n_layers=48,
+    n_heads=32, n_kv_heads=4, n_experts=128, top_k_experts=8)
+# q_size (8 * 16 = 128) != hidden_size (64) on purpose: whatever assumes
+# the two are equal breaks in the tests
+PRESETS["tiny-qwen3"] = ModelSpec(
+    name="tiny-qwen3", vocab_size=512, hidden_size=64, intermediate_size=128,
+    n_layers=2, n_heads=8, n_kv_heads=2, head_dim=16, rope_theta=10000.0,
+    max_seq_len=512, tie_embeddings=True, qk_norm=True,
+)
+PRESETS["tiny-qwen3-moe"] = ModelSpec(
+    **{**PRESETS["tiny-moe"].__dict__, "name": "tiny-qwen3-moe",
+       "qk_norm": True})
+
+
 def _gpt2(name: str, n_layers: int, hidden: int, n_heads: int) -> ModelSpec:
     return ModelSpec(
         name=name,
@@ -390,6 +436,15 @@ _ALIASES = {
     "qwen/qwen2.5-32b": "qwen2.5-32b",
     "qwen/qwen2.5-72b": "qwen2.5-72b",
     "qwen2.5": "qwen2.5-7b",
+    "qwen/qwen3-0.6b": "qwen3-0.6b",
+    "qwen/qwen3-1.7b": "qwen3-1.7b",
+    "qwen/qwen3-4b": "qwen3-4b",
+    "qwen/qwen3-8b": "qwen3-8b",
+    "qwen/qwen3-14b": "qwen3-14b",
+    "qwen/qwen3-32b": "qwen3-32b",
+    "qwen/qwen3-30b-a3b": "qwen3-30b-a3b",
+    "qwen3": "qwen3-8b",
+    "qwen3-moe": "qwen3-30b-a3b",
     "zephyr": "zephyr-7b",
     "zephyr-7b-beta": "zephyr-7b",
     "mistral-7b": "zephyr-7b",
@@ -472,11 +527,31 @@ def spec_from_hf_config(model_path: str, name: Optional[str] = None) -> ModelSpe
         return spec
     n_heads = cfg.get("num_attention_heads", 32)
     hidden = cfg.get("hidden_size", 4096)
+    model_type = cfg.get("model_type")
+    intermediate = cfg.get("intermediate_size", 11008)
+    n_experts = cfg.get("num_local_experts", 0)
+    if model_type == "qwen3_moe":
+        # gating here is softmax -> top-k -> renormalise, on every layer
+        if not cfg.get("norm_topk_prob", False):
+            raise ValueError(
+                "qwen3_moe config with norm_topk_prob false (or absent): "
+                "only renormalised top-k routing is supported")
+        if cfg.get("mlp_only_layers"):
+            raise ValueError(
+                "qwen3_moe config with dense mlp_only_layers "
+                f"{cfg['mlp_only_layers']}: mixed dense/MoE stacks are not "
+                "supported")
+        if cfg.get("decoder_sparse_step", 1) != 1:
+            raise ValueError(
+                "qwen3_moe config with decoder_sparse_step "
+                f"{cfg['decoder_sparse_step']}: every layer must be MoE")
+        n_experts = cfg.get("num_experts", 0)
+        intermediate = cfg.get("moe_intermediate_size", intermediate)
     return ModelSpec(
         name=name or cfg.get("_name_or_path", os.path.basename(model_path)),
         vocab_size=cfg.get("vocab_size", 32000),
         hidden_size=hidden,
-        intermediate_size=cfg.get("intermediate_size", 11008),
+        intermediate_size=intermediate,
         n_layers=cfg.get("num_hidden_layers", 32),
         n_heads=n_heads,
         n_kv_heads=cfg.get("num_key_value_heads", n_heads),
@@ -492,8 +567,9 @@ def spec_from_hf_config(model_path: str, name: Optional[str] = None) -> ModelSpe
             == "llama3" else None
         ),
         sliding_window=_sliding_window_from_cfg(cfg),
-        n_experts=cfg.get("num_local_experts", 0),
+        n_experts=n_experts,
         top_k_experts=cfg.get("num_experts_per_tok", 2),
+        qk_norm=model_type in ("qwen3", "qwen3_moe"),
         # Qwen2 sets attention_bias (or ships q/k/v bias tensors implicitly)
         qkv_bias=bool(
             cfg.get("attention_bias", False)

@@ -15,7 +15,9 @@ transformers — bee2bee/hf.py:23-32):
   model.layers.{i}.mlp.{gate,up,down}_proj.weight,
   model.layers.{i}.{input,post_attention}_layernorm.weight, model.norm.weight,
   lm_head.weight; Mixtral: model.layers.{i}.block_sparse_moe.gate.weight and
-  .experts.{e}.w{1,2,3}.weight.
+  .experts.{e}.w{1,2,3}.weight; Qwen3: model.layers.{i}.self_attn.
+  {q,k}_norm.weight; Qwen3-MoE: model.layers.{i}.mlp.gate.weight and
+  .mlp.experts.{e}.{gate,up,down}_proj.weight.
 """
 from __future__ import annotations
 
@@ -32,7 +34,7 @@ from .spec import ModelSpec
 class LayerWeights:
     __slots__ = (
         "attn_norm", "attn_norm_bias", "wqkv", "wqkv_bias", "wo", "wo_bias",
-        "mlp_norm", "mlp_norm_bias",
+        "mlp_norm", "mlp_norm_bias", "q_norm", "k_norm",
         "w_gate_up", "w_gate_up_bias", "w_down", "w_down_bias",  # dense mlp
         "moe_gate", "moe_w_gate_up", "moe_w_down",  # moe
     )
@@ -42,6 +44,8 @@ class LayerWeights:
         self.attn_norm_bias = None  # layernorm arch (gpt2)
         self.wqkv = None
         self.wqkv_bias = None  # Qwen2/gpt2 fused [q+2kv] bias (optional)
+        self.q_norm = None  # Qwen3 per-head QK-norm weights, [head_dim]
+        self.k_norm = None
         self.wo = None
         self.wo_bias = None
         self.mlp_norm = None
@@ -145,6 +149,13 @@ class ModelWeights:
             if s.norm_type == "layernorm":
                 lw.attn_norm_bias = zeros(s.hidden_size)
                 lw.mlp_norm_bias = zeros(s.hidden_size)
+            if s.qk_norm:
+                # random around 1, and q != k: an all-ones init would hide
+                # a dropped or swapped norm weight from every test
+                lw.q_norm = (1.0 + rnd(f"l{i}.q_norm", s.head_dim,
+                                       std=0.25).float()).to(self.dtype)
+                lw.k_norm = (1.0 + rnd(f"l{i}.k_norm", s.head_dim,
+                                       std=0.25).float()).to(self.dtype)
             lw.wo = rnd(f"l{i}.wo", s.hidden_size, s.q_size, std=proj_std)
             if s.attn_out_bias:
                 lw.wo_bias = zeros(s.hidden_size)
@@ -275,6 +286,17 @@ class ModelWeights:
                 try_fuse(i)
             elif sub == "self_attn.o_proj.weight":
                 lw.wo = to_dev(tensor)
+            elif sub in ("self_attn.q_norm.weight", "self_attn.k_norm.weight"):
+                if not s.qk_norm:
+                    raise ValueError(
+                        f"checkpoint at {model_path} has {name} but its "
+                        "config does not describe a QK-norm (qwen3) model; "
+                        "refusing to drop the tensor")
+                if tuple(tensor.shape) != (s.head_dim,):
+                    raise ValueError(
+                        f"{name}: expected [{s.head_dim}], got "
+                        f"{tuple(tensor.shape)}")
+                setattr(lw, parts[4], to_dev(tensor))
             elif sub in ("self_attn.k_scale", "self_attn.v_scale"):
                 kv_scales[parts[4]][i] = head_scale(name, tensor)
             elif sub == "mlp.gate_proj.weight":
@@ -285,13 +307,17 @@ class ModelWeights:
                 try_fuse(i)
             elif sub == "mlp.down_proj.weight":
                 lw.w_down = to_dev(tensor)
-            elif sub == "block_sparse_moe.gate.weight":
+            elif sub in ("block_sparse_moe.gate.weight", "mlp.gate.weight"):
                 lw.moe_gate = to_dev(tensor)
-            elif parts[3] == "block_sparse_moe" and parts[4] == "experts":
+            elif (parts[3] in ("block_sparse_moe", "mlp")
+                  and parts[4] == "experts"):
                 e = int(parts[5])
                 if not (e_lo <= e < e_hi):
                     continue  # expert owned by another EP rank
-                w = parts[6]  # w1 (gate), w2 (down), w3 (up)
+                # Mixtral w1 (gate), w2 (down), w3 (up); Qwen3-MoE spells
+                # them out as {gate,up,down}_proj
+                w = {"gate_proj": "w1", "down_proj": "w2",
+                     "up_proj": "w3"}.get(parts[6], parts[6])
                 key = f"moe.{i}"
                 pending.setdefault(key, {})[f"{w}.{e}"] = to_dev(tensor)
                 p = pending[key]
@@ -316,6 +342,10 @@ class ModelWeights:
         for i in range(lo, hi):
             if self.layers[i].wqkv is None:
                 missing.append(f"layers.{i}.qkv")
+            if s.qk_norm:
+                for nm in ("q_norm", "k_norm"):
+                    if getattr(self.layers[i], nm) is None:
+                        missing.append(f"layers.{i}.self_attn.{nm}")
         if missing:
             raise FileNotFoundError(
                 f"checkpoint at {model_path} is missing tensors: {missing[:5]}"
@@ -506,17 +536,25 @@ def save_hf(weights: ModelWeights, out_dir: str) -> None:
             tensors[f"{pfx}.self_attn.k_proj.bias"] = cpu(kb)
             tensors[f"{pfx}.self_attn.v_proj.bias"] = cpu(vb)
         tensors[f"{pfx}.self_attn.o_proj.weight"] = cpu(lw.wo)
+        if s.qk_norm:
+            tensors[f"{pfx}.self_attn.q_norm.weight"] = cpu(lw.q_norm)
+            tensors[f"{pfx}.self_attn.k_norm.weight"] = cpu(lw.k_norm)
         tensors[f"{pfx}.input_layernorm.weight"] = cpu(lw.attn_norm)
         tensors[f"{pfx}.post_attention_layernorm.weight"] = cpu(lw.mlp_norm)
         if s.is_moe:
-            tensors[f"{pfx}.block_sparse_moe.gate.weight"] = cpu(lw.moe_gate)
+            # Mixtral names, or Qwen3-MoE names for a QK-norm MoE spec
+            if s.qk_norm:
+                moe, gn, un, dn = "mlp", "gate_proj", "up_proj", "down_proj"
+            else:
+                moe, gn, un, dn = "block_sparse_moe", "w1", "w3", "w2"
+            tensors[f"{pfx}.{moe}.gate.weight"] = cpu(lw.moe_gate)
             for e in range(s.n_experts):
                 g, u = torch.split(
                     lw.moe_w_gate_up[e], [s.intermediate_size, s.intermediate_size], dim=0
                 )
-                tensors[f"{pfx}.block_sparse_moe.experts.{e}.w1.weight"] = cpu(g)
-                tensors[f"{pfx}.block_sparse_moe.experts.{e}.w3.weight"] = cpu(u)
-                tensors[f"{pfx}.block_sparse_moe.experts.{e}.w2.weight"] = cpu(
+                tensors[f"{pfx}.{moe}.experts.{e}.{gn}.weight"] = cpu(g)
+                tensors[f"{pfx}.{moe}.experts.{e}.{un}.weight"] = cpu(u)
+                tensors[f"{pfx}.{moe}.experts.{e}.{dn}.weight"] = cpu(
                     lw.moe_w_down[e]
                 )
         else:
@@ -548,9 +586,21 @@ def save_hf(weights: ModelWeights, out_dir: str) -> None:
     if s.is_moe:
         cfg["num_local_experts"] = s.n_experts
         cfg["num_experts_per_tok"] = s.top_k_experts
+    if s.qk_norm:
+        cfg["model_type"] = "qwen3"
+        cfg["architectures"] = ["Qwen3ForCausalLM"]
+        if s.is_moe:
+            cfg["model_type"] = "qwen3_moe"
+            cfg["architectures"] = ["Qwen3MoeForCausalLM"]
+            del cfg["num_local_experts"]
+            cfg["num_experts"] = s.n_experts
+            cfg["moe_intermediate_size"] = s.intermediate_size
+            cfg["norm_topk_prob"] = True
+            cfg["decoder_sparse_step"] = 1
+            cfg["mlp_only_layers"] = []
     if s.sliding_window:
         cfg["sliding_window"] = int(s.sliding_window)
-        if not s.is_moe and not s.qkv_bias:
+        if not s.is_moe and not s.qkv_bias and not s.qk_norm:
             # the llama config class knows no window: a windowed dense
             # checkpoint is a Mistral one, and loads as such elsewhere
             cfg["model_type"] = "mistral"

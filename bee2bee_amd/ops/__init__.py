@@ -7,7 +7,8 @@ immediately rather than silently falling back to eager PyTorch. The torch
 reference path (ops/reference.py) runs only for CPU tensors (tests and
 GPU-less plumbing runs).
 
-Kernels (ops/csrc/): fused (add+)RMSNorm, RoPE, paged KV store, paged GQA
+Kernels (ops/csrc/): fused (add+)RMSNorm, RoPE, fused per-head QK-norm +
+RoPE (Qwen3), paged KV store, paged GQA
 decode attention (flash-decoding style), MFMA flash prefill attention,
 SwiGLU, top-k gating, grouped expert GEMM. Plain projection GEMMs go
 through hipBLASLt via torch.nn.functional.linear — library GEMMs are the
@@ -109,6 +110,27 @@ def rope_inplace(
         require_hip().rope_inplace(q, k, positions, cos, sin)
         return
     reference.rope_inplace(q, k, positions, cos, sin)
+
+
+def qk_norm_rope_inplace(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    positions: torch.Tensor,
+    cos: torch.Tensor,
+    sin: torch.Tensor,
+    q_weight: torch.Tensor,
+    k_weight: torch.Tensor,
+    eps: float,
+) -> None:
+    """Qwen3: per-head RMSNorm of q and k over head_dim (q_weight /
+    k_weight are [head_dim], shared by all heads), then RoPE — one fused
+    HIP kernel, in place on the strided q/k views."""
+    if _use_hip(q):
+        require_hip().qk_norm_rope_inplace(q, k, positions, cos, sin,
+                                           q_weight, k_weight, eps)
+        return
+    reference.qk_norm_rope_inplace(q, k, positions, cos, sin, q_weight,
+                                   k_weight, eps)
 
 
 def kv_cache_store(

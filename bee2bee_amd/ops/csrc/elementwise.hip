@@ -1,5 +1,5 @@
-// Memory-bound fused kernels: RMSNorm, fused add+RMSNorm, RoPE, SwiGLU,
-// paged-KV store. All bf16 I/O vectorized as short8 (16 B/lane — guide G13:
+// Memory-bound fused kernels: RMSNorm, fused add+RMSNorm, RoPE, per-head
+// QK-norm + RoPE (Qwen3), SwiGLU, paged-KV store. All bf16 I/O vectorized as short8 (16 B/lane — guide G13:
 // hipcc does not auto-vectorize bf16 loads; scalar bf16 is ~2x slower).
 //
 // These replace what the reference ran inside transformers.generate()
@@ -184,6 +184,85 @@ __global__ void rope_kernel(
     }
 }
 
+// ----------------------------------------------------------- qk_norm_rope
+// Qwen3 attention prologue: per-head RMSNorm over head_dim (one [hd] weight
+// for all q heads, another for all k heads), then rotate-half RoPE — fused,
+// in place on the strided q/k views of the fused qkv projection. Same
+// mapping as rope_kernel: one wave per (token, head), lane owns the pairs
+// (d, d + hd/2) for d = lane, lane + 64 (hd <= 256). The head lives in
+// registers as fp32 between the read and the write; the sum of squares is
+// one wave_sum (no LDS, no barrier). Normalise, weight and rotate in fp32;
+// the only bf16 rounding is the store. The early exit is wave-uniform
+// (glob_wave is), so wave_sum always runs with all 64 lanes: lanes past
+// hd/2 add zero to the reduction and store nothing.
+#define QKN_PAIRS 2  // pairs per lane: hd/2 <= QKN_PAIRS * WAVE
+
+__global__ void __launch_bounds__(256) qk_norm_rope_kernel(
+    unsigned short* __restrict__ q,  // [T, nq, hd], token stride sq
+    unsigned short* __restrict__ k,  // [T, nkv, hd], token stride sk
+    const int* __restrict__ pos,     // [T]
+    const float* __restrict__ cos_t, // [max_len, hd/2]
+    const float* __restrict__ sin_t,
+    const unsigned short* __restrict__ qw,  // [hd]
+    const unsigned short* __restrict__ kw,  // [hd]
+    int T, int nq, int nkv, int hd, long sq, long sk, float eps) {
+    // wave-uniform by construction; saying so keeps t, h, the base
+    // pointers and pos[t] in scalar registers
+    const int glob_wave = __builtin_amdgcn_readfirstlane(
+        (int)((blockIdx.x * blockDim.x + threadIdx.x) / WAVE));
+    const int lane = threadIdx.x % WAVE;
+    const int heads = nq + nkv;
+    if (glob_wave >= T * heads) return;
+    const int t = glob_wave / heads;
+    const int h = glob_wave % heads;
+    unsigned short* base = (h < nq) ? q + (long)t * sq + (long)h * hd
+                                    : k + (long)t * sk + (long)(h - nq) * hd;
+    const unsigned short* w = (h < nq) ? qw : kw;
+    const int half = hd / 2;
+    BB_KASSERT(half <= QKN_PAIRS * WAVE);
+    const long tab = (long)pos[t] * half;
+
+    // Every load is issued before the reduction, so the wave pays one
+    // memory latency, not two: tables and weights wait in registers. A lane
+    // past hd/2 reads pair 0 (in bounds) and its values are discarded, so
+    // the loads are straight-line code; only the stores are predicated.
+    float x1[QKN_PAIRS], x2[QKN_PAIRS], c[QKN_PAIRS], s[QKN_PAIRS];
+    float w1[QKN_PAIRS], w2[QKN_PAIRS];
+#pragma unroll
+    for (int i = 0; i < QKN_PAIRS; ++i) {
+        if (i * WAVE >= half) break;  // wave-uniform
+        const int d = lane + i * WAVE;
+        const int dd = d < half ? d : 0;
+        x1[i] = bf2f(base[dd]);
+        x2[i] = bf2f(base[dd + half]);
+        c[i] = cos_t[tab + dd];
+        s[i] = sin_t[tab + dd];
+        w1[i] = bf2f(w[dd]);
+        w2[i] = bf2f(w[dd + half]);
+    }
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < QKN_PAIRS; ++i) {
+        if (i * WAVE >= half) break;
+        const float v = x1[i] * x1[i] + x2[i] * x2[i];
+        ss += (lane + i * WAVE < half) ? v : 0.f;
+    }
+    ss = wave_sum(ss);
+    const float inv = rsqrtf(ss / (float)hd + eps);
+
+#pragma unroll
+    for (int i = 0; i < QKN_PAIRS; ++i) {
+        if (i * WAVE >= half) break;
+        const int d = lane + i * WAVE;
+        if (d < half) {
+            const float n1 = x1[i] * inv * w1[i];
+            const float n2 = x2[i] * inv * w2[i];
+            base[d] = f2bf(n1 * c[i] - n2 * s[i]);
+            base[d + half] = f2bf(n2 * c[i] + n1 * s[i]);
+        }
+    }
+}
+
 // ---------------------------------------------------------- kv_cache_store
 // Scatter new K/V rows into the paged pool. One wave per (token, kv head).
 __global__ void kv_store_kernel(
@@ -349,6 +428,18 @@ void launch_rope(unsigned short* q, unsigned short* k, const int* pos,
     const long blocks = (waves + 3) / 4;
     hipLaunchKernelGGL(rope_kernel, dim3(blocks), dim3(256), 0, stream, q, k,
                        pos, cos_t, sin_t, T, nq, nkv, hd, sq, sk);
+}
+
+void launch_qk_norm_rope(unsigned short* q, unsigned short* k, const int* pos,
+                         const float* cos_t, const float* sin_t,
+                         const unsigned short* qw, const unsigned short* kw,
+                         int T, int nq, int nkv, int hd, long sq, long sk,
+                         float eps, hipStream_t stream) {
+    const long waves = (long)T * (nq + nkv);
+    const long blocks = (waves + 3) / 4;
+    hipLaunchKernelGGL(qk_norm_rope_kernel, dim3(blocks), dim3(256), 0, stream,
+                       q, k, pos, cos_t, sin_t, qw, kw, T, nq, nkv, hd, sq, sk,
+                       eps);
 }
 
 void launch_kv_store(const unsigned short* k, const unsigned short* v,

@@ -27,6 +27,10 @@ void launch_fused_add_layernorm(const unsigned short*, const unsigned short*,
 void launch_gelu(const unsigned short*, unsigned short*, long, hipStream_t);
 void launch_rope(unsigned short*, unsigned short*, const int*, const float*,
                  const float*, int, int, int, int, long, long, hipStream_t);
+void launch_qk_norm_rope(unsigned short*, unsigned short*, const int*,
+                         const float*, const float*, const unsigned short*,
+                         const unsigned short*, int, int, int, int, long,
+                         long, float, hipStream_t);
 void launch_kv_store(const unsigned short*, const unsigned short*,
                      unsigned short*, unsigned short*, const int*, int, int,
                      int, int, long, long, hipStream_t);
@@ -155,6 +159,48 @@ void rope_inplace(Tensor& q, Tensor& k, const Tensor& pos, const Tensor& cos_t,
     launch_rope(bf16p_mut(q), bf16p_mut(k), pos.data_ptr<int>(),
                 cos_t.data_ptr<float>(), sin_t.data_ptr<float>(), T, nq, nkv,
                 hd, q.stride(0), k.stride(0), stream());
+}
+
+// Qwen3 per-head q/k RMSNorm + RoPE, in place. Layout contract of
+// rope_inplace, plus one bf16 [hd] norm weight each for q and k.
+void qk_norm_rope_inplace(Tensor& q, Tensor& k, const Tensor& pos,
+                          const Tensor& cos_t, const Tensor& sin_t,
+                          const Tensor& q_weight, const Tensor& k_weight,
+                          double eps) {
+    check_bf16(q, "q");
+    check_bf16(k, "k");
+    check_bf16(q_weight, "q_weight");
+    check_bf16(k_weight, "k_weight");
+    TORCH_CHECK(q.dim() == 3 && k.dim() == 3,
+                "qk_norm_rope: q and k must be [T, heads, head_dim]");
+    TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == torch::kInt32 &&
+                    pos.dim() == 1 && pos.is_contiguous(),
+                "qk_norm_rope: positions must be int32 [T] on GPU");
+    TORCH_CHECK(cos_t.is_cuda() && sin_t.is_cuda() &&
+                    cos_t.scalar_type() == torch::kFloat32 &&
+                    sin_t.scalar_type() == torch::kFloat32,
+                "qk_norm_rope: cos/sin tables must be fp32 on GPU");
+    const int T = q.size(0);
+    const int nq = q.size(1), nkv = k.size(1), hd = q.size(2);
+    TORCH_CHECK(hd >= 2 && hd % 2 == 0 && hd <= 256,
+                "qk_norm_rope: head_dim must be even and <= 256, got ", hd);
+    TORCH_CHECK(k.size(2) == hd && k.size(0) == T && pos.size(0) == T);
+    // heads/dims contiguous within a token; token stride may be larger
+    TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == hd);
+    TORCH_CHECK(k.stride(2) == 1 && k.stride(1) == hd);
+    TORCH_CHECK(cos_t.dim() == 2 && cos_t.size(1) == hd / 2 &&
+                cos_t.sizes() == sin_t.sizes() && cos_t.is_contiguous() &&
+                sin_t.is_contiguous());
+    for (const Tensor* w : {&q_weight, &k_weight})
+        TORCH_CHECK(w->dim() == 1 && w->size(0) == hd && w->is_contiguous(),
+                    "qk_norm_rope: norm weights must be bf16 [head_dim] "
+                    "contiguous");
+    TORCH_CHECK((long)T * (nq + nkv) <= INT_MAX);
+    if (T == 0 || nq + nkv == 0) return;
+    launch_qk_norm_rope(bf16p_mut(q), bf16p_mut(k), pos.data_ptr<int>(),
+                        cos_t.data_ptr<float>(), sin_t.data_ptr<float>(),
+                        bf16p(q_weight), bf16p(k_weight), T, nq, nkv, hd,
+                        q.stride(0), k.stride(0), (float)eps, stream());
 }
 
 void kv_cache_store(const Tensor& k, const Tensor& v, Tensor& k_cache,
@@ -460,6 +506,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("fused_add_rmsnorm", &fused_add_rmsnorm,
           "residual += x; y = rmsnorm(residual)");
     m.def("rope_inplace", &rope_inplace, "llama RoPE in place");
+    m.def("qk_norm_rope_inplace", &qk_norm_rope_inplace,
+          "per-head q/k RMSNorm + RoPE in place (Qwen3)");
     namespace py = pybind11;
     m.def("kv_cache_store", &kv_cache_store, "paged KV scatter",
           py::arg("k"), py::arg("v"), py::arg("k_cache"), py::arg("v_cache"),

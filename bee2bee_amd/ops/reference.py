@@ -116,6 +116,33 @@ def rope_inplace(
         t[..., hd // 2 :] = (x2 * c + x1 * s).to(t.dtype)
 
 
+def qk_norm_rope_inplace(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    positions: torch.Tensor,
+    cos: torch.Tensor,
+    sin: torch.Tensor,
+    q_weight: torch.Tensor,
+    k_weight: torch.Tensor,
+    eps: float,
+) -> None:
+    """Qwen3 attention prologue: RMSNorm of every q head and every k head
+    over head_dim (one [hd] weight for all q heads, one for all k heads),
+    then rotate-half RoPE. fp32 throughout; the single rounding to the
+    tensor dtype is the final write."""
+    hd = q.shape[-1]
+    pos = positions.long()
+    c = cos[pos].unsqueeze(1).float()  # [T, 1, hd/2]
+    s = sin[pos].unsqueeze(1).float()
+    for t, w in ((q, q_weight), (k, k_weight)):
+        xf = t.detach().clone().float()
+        xf = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
+        xf = xf * w.float()
+        x1, x2 = xf[..., : hd // 2], xf[..., hd // 2 :]
+        t[..., : hd // 2] = (x1 * c - x2 * s).to(t.dtype)
+        t[..., hd // 2 :] = (x2 * c + x1 * s).to(t.dtype)
+
+
 def _kv_deq(cache: torch.Tensor) -> torch.Tensor:
     """Dequantize an fp8 (OCP e4m3, uint8 storage) cache to fp32; bf16/fp32
     caches pass through as fp32."""

@@ -97,6 +97,9 @@ def shard_weights(
                 lw.wqkv_bias[spec.q_size + spec.kv_size + kv_lo :
                              spec.q_size + spec.kv_size + kv_hi],
             ], dim=0).contiguous()
+        # per-head_dim, not per-head: every rank keeps the whole vector
+        ol.q_norm = lw.q_norm
+        ol.k_norm = lw.k_norm
         ol.wo = lw.wo[:, q_lo:q_hi].contiguous()
         ol.w_gate_up = torch.cat(
             [lw.w_gate_up[i_lo:i_hi], lw.w_gate_up[I + i_lo : I + i_hi]],
