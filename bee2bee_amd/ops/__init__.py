@@ -201,6 +201,38 @@ def attn_decode_lse(
         k_scale=k_scale, v_scale=v_scale, window=window)
 
 
+_DECODE_PATHS = {"auto": 0, "split": 1, "fused": 2}
+
+
+def attn_decode_select(
+    q: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    block_table: torch.Tensor,
+    seq_lens: torch.Tensor,
+    scale: float,
+    k_scale: Optional[torch.Tensor] = None,
+    v_scale: Optional[torch.Tensor] = None,
+    window: int = 0,
+    path="auto",
+    max_z: int = 0,
+):
+    """attn_decode_lse with the decode kernels chosen by the caller, for
+    tests and benchmarks. path: "auto", "split" (scores, PV, combine) or
+    "fused" (scores + PV in one kernel, head_dim 64/128 only), or 0/1/2.
+    max_z > 0 caps the chunk-walking blocks per (seq, kv head); max_z=1
+    forces the FOLD kernels. The CPU reference ignores both."""
+    if _use_hip(q):
+        out, ml = require_hip().attn_decode_select(
+            q, k_cache, v_cache, block_table, seq_lens, scale, k_scale,
+            v_scale, window, _DECODE_PATHS.get(path, path), max_z
+        )
+        return out, ml
+    return reference.attn_decode_lse(
+        q, k_cache, v_cache, block_table, seq_lens, scale,
+        k_scale=k_scale, v_scale=v_scale, window=window)
+
+
 def attn_prefill(
     q: torch.Tensor,
     k: torch.Tensor,

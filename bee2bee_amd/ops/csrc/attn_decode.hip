@@ -1,17 +1,22 @@
 // Paged GQA decode attention — three-stage flash-decoding.
 //
 // The decode step is memory-bound on KV reads (per key: 2*hd*2 B moved).
-// A single fused kernel could not reach the HBM roofline: its score phase
-// (lanes-over-keys) and PV phase (lanes-over-dims) have opposing register
-// needs, and together they pushed VGPRs past 100 -> 2 waves/SIMD -> too few
+// The first single fused kernel (VALU lanes-over-keys scores with q in
+// registers, then lanes-over-dims PV) could not reach the HBM roofline: the
+// two phases together pushed VGPRs past 100 -> 2 waves/SIMD -> too few
 // bytes in flight (measured 1.7-2.5 TB/s vs 6.0 TB/s for each access
 // pattern probed in isolation — see probe.hip bw_* kernels). Splitting into
-// per-chunk kernels keeps each at <=64 VGPRs with deep independent-load
-// batches:
+// per-chunk kernels keeps each small, with deep independent-load batches:
 //   1. attn_scores:  S = q.K^T + chunk-level softmax -> p, (m,l) scratch
 //   2. attn_pv:      partial_o = p.V per chunk (p from scratch, LDS-staged)
 //   3. attn_combine: merge chunk partials, normalize, write bf16 out
 // Scratch p traffic is ~3% of KV traffic.
+//
+// attn_decode_fused_kernel (hd 64/128) is stages 1 and 2 in one launch,
+// built from the MFMA scores kernel and the LDS-state FOLD PV kernel: p
+// stays in LDS, and the result is bit for bit the split path's. It holds
+// 4 waves/SIMD with no scratch. launch_attn_decode picks between the two
+// (attn_decode_plan; measurements in docs/KERNELS.md, "Fused scores + PV").
 //
 // Per-kv-head fp8 scales (scaled fp8 cache, value = float(byte)*scale[h]):
 // k_scale multiplies the fp32 SCORE after the dot product / MFMA (never the
@@ -910,6 +915,398 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_decode_combine_kernel(
     }
 }
 
+// ------------------------------------------- fused scores + PV (hd 64/128)
+// attn_scores_mfma_kernel and attn_pv_kernel in one launch: per chunk the
+// block runs the MFMA scores + chunk softmax, leaves p in LDS in the
+// [key][G] fp32 layout the PV loop reads, and goes straight on to the PV
+// phase. Every floating-point expression is the split path's, in the split
+// path's order, so out / out_ml (and part_o / part_ml without FOLD) are bit
+// for bit what the two kernels produce. What the fusion drops:
+//   - the bf16 p scratch round trip through HBM and the part_ml re-read;
+//   - the second launch with its own fill/drain and seq_lens / block-table
+//     reads: a key's page is looked up once by the thread that owns the key
+//     and reaches the K-fragment rows by a wave shuffle (K and V caches
+//     share one layout, so the same page serves the V row offset);
+//   - the single-thread (m, l) tail: the wave that owns head g reduces the
+//     chunk's (m, l) from `red` itself at fold time (same order of sums);
+//   - one barrier: the max and sum slots of `red` are distinct words.
+// LDS: the PV kernel's layout, then q_s and red (q_s is dead once the B
+// fragments are built).
+// The two phases run one after the other and each fits 4 waves/SIMD on its
+// own, but nothing tells the compiler so: left alone it allocated 285
+// registers, and with the occupancy asked for it kept every lane-derived
+// index and the B fragments live across the PV loop and spilled them. So
+// each phase derives its indices from phase_tid(), a thread id the
+// optimizer cannot see through, and the B fragments are rebuilt from q_s
+// every chunk: nothing but scalars lives from one phase to the next.
+__device__ __forceinline__ int phase_tid() {
+    int t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    return t;
+}
+
+template <int G, int HD, bool FOLD, typename KVT, bool SCALED, bool WINDOWED>
+__global__ __launch_bounds__(DEC_BLOCK)
+__attribute__((amdgpu_waves_per_eu(4))) void attn_decode_fused_kernel(
+    const unsigned short* __restrict__ q,        // [B, nq, HD] (strided)
+    const KVT* __restrict__ k_cache,             // [nb, nkv, bs, HD]
+    const KVT* __restrict__ v_cache,             // [nb, nkv, bs, HD]
+    const int* __restrict__ block_table,         // [B, W]
+    const int* __restrict__ seq_lens,            // [B]
+    float* __restrict__ part_o,                  // [B, nkv, C, G, HD] (!FOLD)
+    float* __restrict__ part_ml,                 // [B, nkv, C, G, 2]  (!FOLD)
+    unsigned short* __restrict__ out,            // [B, nq, HD] (FOLD)
+    float* __restrict__ out_ml,                  // optional [B, nq, 2] (FOLD)
+    int nkv, int W, int bs, int C, long q_stride, float scale,
+    const float* __restrict__ k_scale,           // [nkv]; read iff SCALED
+    const float* __restrict__ v_scale,           // [nkv]; read iff SCALED
+    int window) {                                // read iff WINDOWED
+    constexpr int KSTEPS = HD / 32;
+    constexpr int TILES = WAVE / 16;  // 4 key-tiles of 16 per wave
+    const int b = blockIdx.x;
+    const int kvh = blockIdx.y;
+    const int nq = nkv * G;
+    const int L = seq_lens[b];
+    const int lo = WINDOWED ? max(0, L - window) : 0;  // first live key
+    const int c0 = WINDOWED ? lo / DEC_CHUNK : 0;      // first live chunk
+    if ((c0 + (int)blockIdx.z) * DEC_CHUNK >= L) {
+        // FOLD (gridDim.z == 1) owns the out rows: an empty sequence gets
+        // what ops/reference.py returns, zeros and (m, l) = (-1e30, 0).
+        // Without FOLD the combine kernel does the same.
+        if (FOLD && L <= 0) {
+            unsigned short* orow = out + ((long)b * nq + kvh * G) * HD;
+            for (int i = threadIdx.x; i < G * HD; i += DEC_BLOCK) orow[i] = 0;
+            if (out_ml != nullptr && threadIdx.x < G) {
+                float* mlrow =
+                    out_ml + ((long)b * nq + kvh * G + threadIdx.x) * 2;
+                mlrow[0] = -1e30f;
+                mlrow[1] = 0.f;
+            }
+        }
+        return;
+    }
+    float ksc = 1.f, vsc = 1.f;
+    if (SCALED) {  // uniform: scalar loads
+        ksc = k_scale[kvh];
+        vsc = v_scale[kvh];
+    }
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    float* p_s = reinterpret_cast<float*>(smem_raw);  // [CHUNK][G]
+    long* voff_s = reinterpret_cast<long*>(p_s + DEC_CHUNK * G);  // [CHUNK]
+    float* merge = reinterpret_cast<float*>(voff_s + DEC_CHUNK);  // [Wv][G][HD]
+    float* run = merge + DEC_WAVES * G * HD;   // [G][HD] running acc (FOLD)
+    unsigned short* q_s = reinterpret_cast<unsigned short*>(run + G * HD);
+    float* red = reinterpret_cast<float*>(
+        reinterpret_cast<char*>(q_s) + ((G * HD * 2 + 15) & ~15));
+    // red: [DEC_WAVES][G][2] wave-level max / sum of the current chunk
+    float* runml = red + DEC_WAVES * G * 2;    // [G][2] running (m, l) (FOLD)
+
+    // q staging: attn_scores_mfma_kernel's, including the SCALED lift
+    {
+    const int lane = threadIdx.x % WAVE;
+    const int wid = threadIdx.x / WAVE;
+    if (SCALED) {
+        float amax = 0.f;
+        for (int i = threadIdx.x; i < G * HD; i += DEC_BLOCK) {
+            const int g = i / HD, d = i % HD;
+            amax = fmaxf(amax, fabsf(bf2f(f2bf(
+                bf2f(q[(long)b * q_stride + (kvh * G + g) * (long)HD + d]) *
+                scale))));
+        }
+        amax = wave_max(amax);
+        if (lane == 0) red[wid] = amax;
+        __syncthreads();
+        amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+        const int e = __builtin_amdgcn_readfirstlane(
+            (__float_as_int(amax) >> 23) & 0xff);
+        float qmul = 1.f;
+        if (e >= 8 && e < 122) {  // amax < 2^-5; 2^-k stays a normal float
+            qmul = __int_as_float((261 - e) << 23);  // 2^(134 - e)
+            ksc *= __int_as_float((e - 7) << 23);    // 2^(e - 134)
+        }
+        for (int i = threadIdx.x; i < G * HD; i += DEC_BLOCK) {
+            const int g = i / HD, d = i % HD;
+            q_s[i] = f2bf(bf2f(f2bf(
+                bf2f(q[(long)b * q_stride + (kvh * G + g) * (long)HD + d]) *
+                scale)) * qmul);
+        }
+    } else {
+        for (int i = threadIdx.x; i < G * HD; i += DEC_BLOCK) {
+            const int g = i / HD, d = i % HD;
+            q_s[i] = f2bf(bf2f(
+                q[(long)b * q_stride + (kvh * G + g) * (long)HD + d]) * scale);
+        }
+    }
+    if (FOLD) {  // head g's running state is owned by wave g % DEC_WAVES
+        for (int g = wid; g < G; g += DEC_WAVES) {
+            for (int i = lane; i < HD; i += WAVE) run[g * HD + i] = 0.f;
+            if (lane == 0) {
+                runml[g * 2] = -1e30f;
+                runml[g * 2 + 1] = 0.f;
+            }
+        }
+    }
+    }
+    __syncthreads();
+
+    using kfrag_t = typename kfrag_of<KVT>::type;
+    const int* bt = block_table + (long)b * W;
+    for (int chunk = c0 + blockIdx.z; chunk * DEC_CHUNK < L;
+         chunk += gridDim.z) {
+    const int start = chunk * DEC_CHUNK;
+    {  // ---- scores phase
+    const int tid = phase_tid();
+    const int lane = tid % WAVE;
+    const int wid = tid / WAVE;
+    const int lg = lane >> 4;  // lane group 0..3
+    const int li = lane & 15;
+    const int wave_start = wid * WAVE;
+    const int wave_key0 = start + wave_start;  // this wave covers 64 keys
+
+    // 1. addresses: thread t owns key start + t. One block-table lookup per
+    // live key; a key past L or below the window is never looked up (its
+    // entry may be stale) and keeps row offset 0.
+    int page = 0;
+    {
+        const int key = start + tid;
+        long voff = 0;
+        if (key < L && (!WINDOWED || key >= lo)) {
+            page = bt[key / bs];
+            BB_KASSERT(page >= 0);  // block table row must be fully mapped
+            voff = (((long)page * nkv + kvh) * bs + key % bs) * HD;
+        }
+        voff_s[tid] = voff;
+    }
+
+    // B-fragments: col = q head (li), k = dim lg*8+e within each kstep.
+    // Rebuilt from q_s every chunk (KSTEPS LDS reads) so that they are not
+    // live across the PV phase, which needs the registers.
+    kfrag_t bq[KSTEPS];
+#pragma unroll
+    for (int ks = 0; ks < KSTEPS; ++ks) {
+        if (li < G) {
+            bq[ks] = qfrag_from_lds<KVT>(q_s + li * HD + ks * 32 + lg * 8);
+        } else {
+            bq[ks] = kfrag_t{};
+        }
+    }
+
+    // K: all TILES*KSTEPS A-fragments issue before any MFMA. Row li of
+    // tile t is key wave_key0 + t*16 + li, owned by lane t*16 + li of this
+    // wave.
+    f32x4 acc[TILES];
+    kfrag_t afr[TILES][KSTEPS];
+#pragma unroll
+    for (int t = 0; t < TILES; ++t) {
+        const int key = wave_key0 + t * 16 + li;  // A row = li
+        const int pg = __shfl(page, t * 16 + li);
+        const KVT* kr;
+        if (key < L && (!WINDOWED || key >= lo)) {
+            kr = k_cache + (((long)pg * nkv + kvh) * bs + key % bs) * HD;
+        } else {
+            kr = k_cache;  // safe dummy row; masked by the score mask below
+        }
+#pragma unroll
+        for (int ks = 0; ks < KSTEPS; ++ks)
+            afr[t][ks] = load_kfrag<KVT>(kr + ks * 32 + lg * 8);
+    }
+#pragma unroll
+    for (int t = 0; t < TILES; ++t) {
+        f32x4 c{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < KSTEPS; ++ks)
+            c = mfma_kq(afr[t][ks], bq[ks], c);
+        acc[t] = c;
+    }
+
+    // 2. scores + chunk softmax. This lane holds scores for g = li, keys
+    // (t*16 + lg*4 + r)
+    float sv[TILES * 4];
+    float lmax = -1e30f;
+#pragma unroll
+    for (int t = 0; t < TILES; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int key = wave_key0 + t * 16 + lg * 4 + r;
+            const bool live = key < L && (!WINDOWED || key >= lo);
+            float v = live ? (SCALED ? acc[t][r] * ksc : acc[t][r])
+                           : -1e30f;
+            sv[t * 4 + r] = v;
+            lmax = fmaxf(lmax, v);
+        }
+    }
+    lmax = fmaxf(lmax, __shfl_xor(lmax, 16));
+    lmax = fmaxf(lmax, __shfl_xor(lmax, 32));
+    if (lg == 0 && li < G) red[(wid * G + li) * 2] = lmax;
+    __syncthreads();
+    float M = -1e30f;  // chunk max for this lane's g
+    if (li < G) {
+#pragma unroll
+        for (int w2 = 0; w2 < DEC_WAVES; ++w2)
+            M = fmaxf(M, red[(w2 * G + li) * 2]);
+    }
+    float lsum = 0.f;
+#pragma unroll
+    for (int i = 0; i < TILES * 4; ++i) {
+        // round to bf16 BEFORE summing so l matches the p that PV consumes
+        const float pv =
+            (sv[i] <= -1e29f) ? 0.f : bf2f(f2bf(__expf(sv[i] - M)));
+        sv[i] = pv;
+        lsum += pv;
+    }
+    lsum += __shfl_xor(lsum, 16);
+    lsum += __shfl_xor(lsum, 32);
+    if (li < G) {
+        if (lg == 0) red[(wid * G + li) * 2 + 1] = lsum;
+        // p stays in LDS, already bf16-rounded, widened for the fma loop
+#pragma unroll
+        for (int t = 0; t < TILES; ++t) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int key = wave_start + t * 16 + lg * 4 + r;
+                p_s[key * G + li] = sv[t * 4 + r];
+            }
+        }
+    }
+    }  // scores phase
+    __syncthreads();
+
+    // 3. PV (attn_pv_kernel's loop): wave wid accumulates the live keys
+    // [kfirst, nkeys) of its 64-key slice; lane owns output dims (d0, d0+1)
+    const int tid = phase_tid();
+    const int lane = tid % WAVE;
+    const int wid = tid / WAVE;
+    const int wave_start = wid * WAVE;
+    const int wave_key0 = start + wave_start;
+    const int d0 = lane * 2;
+    const int nkeys = min(WAVE, L - wave_key0);
+    const int kfirst = WINDOWED ? min(WAVE, max(0, lo - wave_key0)) : 0;
+    float o0[G], o1[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) o0[g] = o1[g] = 0.f;
+    if (d0 < HD && nkeys > kfirst) {
+        const long* voffs = voff_s + wave_start;
+        const float* pw = p_s + wave_start * G;
+        int t = kfirst;
+        for (; t + 32 <= nkeys; t += 32) {  // 32 V loads in flight
+            kv_pair_t<KVT> vv[32];
+#pragma unroll
+            for (int j = 0; j < 32; ++j)
+                vv[j] = *reinterpret_cast<const kv_pair_t<KVT>*>(
+                    v_cache + voffs[t + j] + d0);
+#pragma unroll
+            for (int j = 0; j < 32; ++j) {
+                const float2v vf = kv_pair_f32(vv[j]);
+                const float* pt = pw + (t + j) * G;
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    o0[g] = fmaf(pt[g], vf.x, o0[g]);
+                    o1[g] = fmaf(pt[g], vf.y, o1[g]);
+                }
+            }
+        }
+        for (; t < nkeys; ++t) {
+            const kv_pair_t<KVT> vv =
+                *reinterpret_cast<const kv_pair_t<KVT>*>(
+                    v_cache + voffs[t] + d0);
+            const float2v vf = kv_pair_f32(vv);
+            const float* pt = pw + t * G;
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                o0[g] = fmaf(pt[g], vf.x, o0[g]);
+                o1[g] = fmaf(pt[g], vf.y, o1[g]);
+            }
+        }
+    }
+
+    // all waves used the same chunk max, so cross-wave merge is a plain sum
+    float* mw = merge + wid * G * HD;
+    if (d0 < HD) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            mw[g * HD + d0] = o0[g];
+            mw[g * HD + d0 + 1] = o1[g];
+        }
+    }
+    __syncthreads();
+    if (d0 < HD) {
+        const long base = (((long)b * nkv + kvh) * C + chunk) * G;
+        for (int g = wid; g < G; g += DEC_WAVES) {
+            float a0 = 0.f, a1 = 0.f;
+            for (int w2 = 0; w2 < DEC_WAVES; ++w2) {
+                a0 += merge[(w2 * G + g) * HD + d0];
+                a1 += merge[(w2 * G + g) * HD + d0 + 1];
+            }
+            // this chunk's (m, l), reduced over the waves in the order of
+            // the scores kernel's tail (wave-uniform LDS reads)
+            float lc = 0.f;
+            for (int w2 = 0; w2 < DEC_WAVES; ++w2)
+                lc += red[(w2 * G + g) * 2 + 1];
+            float mc = -1e30f;
+            for (int w2 = 0; w2 < DEC_WAVES; ++w2)
+                mc = fmaxf(mc, red[(w2 * G + g) * 2]);
+            if (FOLD) {
+                const float mold = runml[g * 2];
+                const float mn = fmaxf(mold, mc);
+                const float alpha = __expf(mold - mn);
+                const float beta = __expf(mc - mn);
+                run[g * HD + d0] = run[g * HD + d0] * alpha + a0 * beta;
+                run[g * HD + d0 + 1] =
+                    run[g * HD + d0 + 1] * alpha + a1 * beta;
+                if (lane == 0) {
+                    runml[g * 2] = mn;
+                    runml[g * 2 + 1] = runml[g * 2 + 1] * alpha + lc * beta;
+                }
+            } else {
+                if (SCALED) {  // per-head V dequant scale, once
+                    a0 *= vsc;
+                    a1 *= vsc;
+                }
+                float* po = part_o + (base + g) * HD;
+                po[d0] = a0;
+                po[d0 + 1] = a1;
+                if (lane == 0) {
+                    part_ml[(base + g) * 2] = mc;
+                    part_ml[(base + g) * 2 + 1] = lc;
+                }
+            }
+        }
+    }
+    __syncthreads();  // LDS buffers reused by the next chunk iteration
+    }  // chunk loop
+
+    // 4. epilogue
+    if (FOLD) {
+        const int tid = phase_tid();
+        const int lane = tid % WAVE;
+        const int wid = tid / WAVE;
+        const int d0f = lane * 2;
+        if (d0f < HD) {
+            for (int g = wid; g < G; g += DEC_WAVES) {
+                const float lr = runml[g * 2 + 1];
+                const float inv = (lr > 0.f) ? 1.f / lr : 0.f;
+                unsigned short* orow =
+                    out + ((long)b * nq + kvh * G + g) * HD;
+                float r0 = run[g * HD + d0f] * inv;
+                float r1 = run[g * HD + d0f + 1] * inv;
+                if (SCALED) {  // per-head V dequant scale, once
+                    r0 *= vsc;
+                    r1 *= vsc;
+                }
+                orow[d0f] = f2bf(r0);
+                orow[d0f + 1] = f2bf(r1);
+            }
+        }
+        if (out_ml != nullptr && lane == 0) {
+            for (int g = wid; g < G; g += DEC_WAVES) {
+                float* mlrow = out_ml + ((long)b * nq + kvh * G + g) * 2;
+                mlrow[0] = runml[g * 2];
+                mlrow[1] = runml[g * 2 + 1];
+            }
+        }
+    }
+}
+
 // MFMA scores launch: SCALED only exists for the fp8 cache type
 template <int G, int HD, typename KVT, bool WIN>
 static void launch_scores_mfma(
@@ -933,9 +1330,77 @@ static void launch_scores_mfma(
                        q_stride, scale, nullptr, window);
 }
 
+// fused launch: FOLD iff one block walks every chunk of its (b, kvh)
+template <int G, int HD, typename KVT, bool WIN>
+static void launch_fused(
+    dim3 grid, int smem, hipStream_t stream, const unsigned short* q,
+    const KVT* kc, const KVT* vc, const int* block_table,
+    const int* seq_lens, float* part_o, float* part_ml, unsigned short* out,
+    float* out_ml, int nkv, int W, int bs, int C, long q_stride, float scale,
+    const float* k_scale, const float* v_scale, int window) {
+#define FUSED_GO(FOLD, SC)                                                     \
+    hipLaunchKernelGGL(                                                        \
+        (attn_decode_fused_kernel<G, HD, FOLD, KVT, SC, WIN>), grid,           \
+        dim3(DEC_BLOCK), smem, stream, q, kc, vc, block_table, seq_lens,       \
+        part_o, part_ml, out, out_ml, nkv, W, bs, C, q_stride, scale,          \
+        k_scale, v_scale, window)
+    const bool fold = grid.z == 1;
+    if constexpr (sizeof(KVT) == 1) {
+        if (k_scale != nullptr) {
+            if (fold) FUSED_GO(true, true);
+            else FUSED_GO(false, true);
+            return;
+        }
+    }
+    if (fold) FUSED_GO(true, false);
+    else FUSED_GO(false, false);
+#undef FUSED_GO
+}
+
+// MFMA PV (attn_pv_mfma_kernel) measured 4.2 TB/s vs the VALU PV's 4.5 at
+// B768/G4: the barrier-paced LDS pipeline loses more latency hiding than
+// the matrix pipe saves (PV is latency-, not VALU-bound). Kept as opt-in
+// infrastructure for future tr_b16 staging work. It knows no window: a
+// windowed launch takes the VALU PV path.
+static bool pv_mfma_enabled() {
+    static int pv_mfma = -1;
+    if (pv_mfma < 0) {
+        const char* e = getenv("BEE2BEE_PV_MFMA");
+        pv_mfma = (e != nullptr && e[0] == '1') ? 1 : 0;
+    }
+    return pv_mfma == 1;
+}
+
+// Which kernels a decode launch takes, for the launcher and for the caller
+// that sizes the scratch: Z chunk-walkers per (b, kvh), and whether the
+// fused scores + PV kernel runs. path: 0 = auto, 1 = split, 2 = fused (the
+// caller rejects 2 for hd other than 64/128). max_z: 0 = the rule below,
+// n = cap Z at n. Auto is fused per cache type where it was measured
+// faster at the flagship shape (docs/KERNELS.md, "Fused scores + PV").
+#define DEC_FUSED_AUTO_BF16 1
+#define DEC_FUSED_AUTO_FP8 1
+extern "C" void attn_decode_plan(int B, int nkv, int hd, int C, int fp8,
+                                 int path, int max_z, int* Z_out,
+                                 int* fused_out) {
+    // enough blocks to fill the chip, but chunks loop within a block so the
+    // cold-start/tail phases amortize over multiple 64 KB K/V bursts
+    int Z = (4096 + B * nkv - 1) / (B * nkv);
+    if (Z > C) Z = C;
+    if (max_z > 0 && Z > max_z) Z = max_z;
+    if (Z < 1) Z = 1;
+    *Z_out = Z;
+    const bool can = hd == 64 || hd == 128;
+    if (path == 0)
+        *fused_out = can && !pv_mfma_enabled() &&
+                     (fp8 ? DEC_FUSED_AUTO_FP8 : DEC_FUSED_AUTO_BF16);
+    else
+        *fused_out = path == 2 && can;
+}
+
 // window > 0: sliding-window attention, keys [max(0, L - window), L) are
 // live. It selects the WINDOWED instantiations; window == 0 launches the
 // same code as before the window existed (the flag folds lo and c0 to 0).
+// The fused path reads neither p_buf nor, with Z == 1, part_o / part_ml.
 extern "C" void launch_attn_decode(
     const unsigned short* q, const void* k_cache, const void* v_cache,
     const int* block_table, const int* seq_lens, unsigned short* p_buf,
@@ -943,12 +1408,10 @@ extern "C" void launch_attn_decode(
     int B, int nkv,
     int G, int W, int bs, int hd, int C, long q_stride, float scale,
     int fp8, const float* k_scale, const float* v_scale, int window,
-    hipStream_t stream) {
-    // enough blocks to fill the chip, but chunks loop within a block so the
-    // cold-start/tail phases amortize over multiple 64 KB K/V bursts
-    int Z = (4096 + B * nkv - 1) / (B * nkv);
-    if (Z > C) Z = C;
-    if (Z < 1) Z = 1;
+    int path, int max_z, hipStream_t stream) {
+    int Z, fused;
+    attn_decode_plan(B, nkv, hd, C, fp8, path, max_z, &Z, &fused);
+    const bool pv_mfma = pv_mfma_enabled();
     dim3 grid(B, nkv, Z);
     dim3 cgrid(B, nkv, G);
     const int smem_s = ((G * hd * 2 + 15) & ~15) + DEC_WAVES * G * 2 * 4;
@@ -957,20 +1420,29 @@ extern "C" void launch_attn_decode(
                         G * hd * 4 + G * 8;  // + FOLD running state
     const int smem_pvm = ((G * (DEC_CHUNK + 8) * 2 + 15) & ~15) +
                          DEC_CHUNK * 8 + 2 * hd * PVM_STRIDE * 2;
-    // MFMA PV (attn_pv_mfma_kernel) measured 4.2 TB/s vs the VALU PV's
-    // 4.5 at B768/G4: the barrier-paced LDS pipeline loses more latency
-    // hiding than the matrix pipe saves (PV is latency-, not VALU-bound).
-    // Kept as opt-in infrastructure for future tr_b16 staging work. It
-    // knows no window: a windowed launch takes the VALU PV path.
-    static int pv_mfma = -1;
-    if (pv_mfma < 0) {
-        const char* e = getenv("BEE2BEE_PV_MFMA");
-        pv_mfma = (e != nullptr && e[0] == '1') ? 1 : 0;
-    }
+    const int smem_f = smem_pv + smem_s;  // G16/hd128: 64128 B
 #define LAUNCH_T(GG, KVT, WIN)                                                 \
     do {                                                                       \
         const KVT* kc = reinterpret_cast<const KVT*>(k_cache);                 \
         const KVT* vc = reinterpret_cast<const KVT*>(v_cache);                 \
+        if (fused) {                                                           \
+            if (hd == 128)                                                     \
+                launch_fused<GG, 128, KVT, WIN>(                               \
+                    grid, smem_f, stream, q, kc, vc, block_table, seq_lens,    \
+                    part_o, part_ml, out, out_ml, nkv, W, bs, C, q_stride,     \
+                    scale, k_scale, v_scale, window);                          \
+            else                                                               \
+                launch_fused<GG, 64, KVT, WIN>(                                \
+                    grid, smem_f, stream, q, kc, vc, block_table, seq_lens,    \
+                    part_o, part_ml, out, out_ml, nkv, W, bs, C, q_stride,     \
+                    scale, k_scale, v_scale, window);                          \
+            if (Z > 1)                                                         \
+                hipLaunchKernelGGL((attn_decode_combine_kernel<GG, WIN>),      \
+                                   cgrid, dim3(DEC_BLOCK), 0, stream, part_o,  \
+                                   part_ml, seq_lens, out, out_ml, nkv, hd, C, \
+                                   window);                                    \
+            break;                                                             \
+        }                                                                      \
         if (hd == 128)                                                         \
             launch_scores_mfma<GG, 128, KVT, WIN>(                             \
                 grid, smem_s, stream, q, kc, block_table, seq_lens, p_buf,     \

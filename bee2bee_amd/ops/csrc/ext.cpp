@@ -44,7 +44,8 @@ void launch_attn_decode(const unsigned short*, const void*, const void*,
                         const int*, const int*, unsigned short*, float*,
                         float*, unsigned short*, float*, int, int, int, int,
                         int, int, int, long, float, int, const float*,
-                        const float*, int, hipStream_t);
+                        const float*, int, int, int, hipStream_t);
+void attn_decode_plan(int, int, int, int, int, int, int, int*, int*);
 void launch_attn_prefill(const unsigned short*, const unsigned short*,
                          const unsigned short*, const int*, unsigned short*,
                          int, int, int, int, long, long, long, int, float,
@@ -295,8 +296,13 @@ std::vector<Tensor> attn_decode_impl(const Tensor& q, const Tensor& k_cache,
                                      const Tensor& seq_lens, double scale,
                                      const OptTensor& k_scale,
                                      const OptTensor& v_scale,
-                                     int64_t window, bool want_lse) {
+                                     int64_t window, bool want_lse,
+                                     int64_t path = 0, int64_t max_z = 0) {
     check_bf16(q, "q");
+    TORCH_CHECK(path >= 0 && path <= 2,
+                "attn_decode: path is 0 (auto), 1 (split) or 2 (fused)");
+    TORCH_CHECK(max_z >= 0 && max_z <= INT_MAX,
+                "attn_decode: max_z must be >= 0 (0 = no cap)");
     TORCH_CHECK(window >= 0 && window <= INT_MAX,
                 "attn_decode: window must be >= 0 (0 = off)");
     const bool scaled =
@@ -322,10 +328,21 @@ std::vector<Tensor> attn_decode_impl(const Tensor& q, const Tensor& k_cache,
     const int kDecChunk = 256;  // keep in sync with DEC_CHUNK
     const int C = (W * bs + kDecChunk - 1) / kDecChunk;
     TORCH_CHECK(C <= 128, "decode supports up to 32768-token contexts for now");
+    TORCH_CHECK(path != 2 || hd == 64 || hd == 128,
+                "attn_decode: the fused kernel supports head_dim 64 and 128, "
+                "got ", hd);
+    int Z = 1, fused = 0;
+    attn_decode_plan(B, nkv, hd, C, fp8 ? 1 : 0, (int)path, (int)max_z, &Z,
+                     &fused);
     auto fopt = q.options().dtype(torch::kFloat32);
-    Tensor p_buf = torch::empty({B, nkv, C, kDecChunk, G}, q.options());
-    Tensor part_o = torch::empty({B, nkv, C, G, hd}, fopt);
-    Tensor part_ml = torch::empty({B, nkv, C, G, 2}, fopt);
+    // the fused kernel keeps p in LDS, and with Z == 1 (FOLD) writes out
+    // directly: no scratch at all
+    Tensor p_buf, part_o, part_ml;
+    if (!fused) p_buf = torch::empty({B, nkv, C, kDecChunk, G}, q.options());
+    if (!fused || Z > 1) {
+        part_o = torch::empty({B, nkv, C, G, hd}, fopt);
+        part_ml = torch::empty({B, nkv, C, G, 2}, fopt);
+    }
     Tensor out_ml;
     float* out_ml_p = nullptr;
     if (want_lse) {
@@ -334,13 +351,14 @@ std::vector<Tensor> attn_decode_impl(const Tensor& q, const Tensor& k_cache,
     }
     launch_attn_decode(bf16p(q), k_cache.data_ptr(), v_cache.data_ptr(),
                        block_table.data_ptr<int>(), seq_lens.data_ptr<int>(),
-                       bf16p_mut(p_buf), part_o.data_ptr<float>(),
-                       part_ml.data_ptr<float>(),
+                       p_buf.defined() ? bf16p_mut(p_buf) : nullptr,
+                       part_o.defined() ? part_o.data_ptr<float>() : nullptr,
+                       part_ml.defined() ? part_ml.data_ptr<float>() : nullptr,
                        bf16p_mut(out), out_ml_p, B, nkv, G, W, bs, hd, C,
                        q.stride(0), (float)scale, fp8 ? 1 : 0,
                        scaled ? k_scale->data_ptr<float>() : nullptr,
                        scaled ? v_scale->data_ptr<float>() : nullptr,
-                       (int)window, stream());
+                       (int)window, (int)path, (int)max_z, stream());
     if (want_lse) return {out, out_ml};
     return {out};
 }
@@ -365,6 +383,23 @@ std::vector<Tensor> attn_decode_lse(const Tensor& q, const Tensor& k_cache,
                                     int64_t window) {
     return attn_decode_impl(q, k_cache, v_cache, block_table, seq_lens,
                             scale, k_scale, v_scale, window, true);
+}
+
+// attn_decode_lse with the kernel path chosen by the caller: path 0 = auto,
+// 1 = split (scores, PV, combine), 2 = fused scores + PV; max_z > 0 caps the
+// chunk-walkers per (seq, kv head), so max_z = 1 forces the FOLD kernels.
+// For tests and benchmarks; serving calls attn_decode / attn_decode_lse.
+std::vector<Tensor> attn_decode_select(const Tensor& q, const Tensor& k_cache,
+                                       const Tensor& v_cache,
+                                       const Tensor& block_table,
+                                       const Tensor& seq_lens, double scale,
+                                       const OptTensor& k_scale,
+                                       const OptTensor& v_scale,
+                                       int64_t window, int64_t path,
+                                       int64_t max_z) {
+    return attn_decode_impl(q, k_cache, v_cache, block_table, seq_lens,
+                            scale, k_scale, v_scale, window, true, path,
+                            max_z);
 }
 
 Tensor attn_prefill(const Tensor& q, const Tensor& k, const Tensor& v,
@@ -529,6 +564,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("block_table"), py::arg("seq_lens"), py::arg("scale"),
           py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none(),
           py::arg("window") = 0);
+    m.def("attn_decode_select", &attn_decode_select,
+          "attn_decode_lse with an explicit kernel path and Z cap",
+          py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+          py::arg("block_table"), py::arg("seq_lens"), py::arg("scale"),
+          py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none(),
+          py::arg("window") = 0, py::arg("path") = 0, py::arg("max_z") = 0);
     m.def("attn_prefill", &attn_prefill, "varlen causal flash prefill",
           py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_seqlens"),
           py::arg("max_seqlen"), py::arg("scale"), py::arg("causal"),

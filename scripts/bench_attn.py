@@ -35,6 +35,10 @@ def main():
     ap.add_argument("--window", type=int, default=0,
                     help="sliding-window attention over the last N keys "
                          "(0 = off), decode and --prefill")
+    ap.add_argument("--path", choices=("auto", "split", "fused"),
+                    default="auto",
+                    help="decode kernels: the launcher's choice, the split "
+                         "scores / PV kernels, or the fused kernel")
     args = ap.parse_args()
     wkw = {"window": args.window} if args.window > 0 else {}
     if args.fp8_scaled:
@@ -97,12 +101,16 @@ def main():
         }
 
     kw.update(wkw)
+    decode = ops.attn_decode
+    if args.path != "auto":
+        def decode(*a, **k):
+            return ops.attn_decode_select(*a, path=args.path, **k)[0]
     for _ in range(5):
-        out = ops.attn_decode(q, kc, vc, bt, lens, scale, **kw)
+        out = decode(q, kc, vc, bt, lens, scale, **kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.iters):
-        out = ops.attn_decode(q, kc, vc, bt, lens, scale, **kw)
+        out = decode(q, kc, vc, bt, lens, scale, **kw)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.iters
     live = min(L, args.window) if args.window > 0 else L  # keys read
@@ -111,7 +119,8 @@ def main():
         f"decode{' fp8' if args.fp8 else ''}"
         f"{'-scaled' if args.fp8_scaled else ''} "
         f"B{B} L{L} nkv{nkv} G{G} hd{hd}"
-        f"{f' w{args.window}' if args.window > 0 else ''}: "
+        f"{f' w{args.window}' if args.window > 0 else ''}"
+        f"{f' path={args.path}' if args.path != 'auto' else ''}: "
         f"{dt * 1e6:.1f} us  "
         f"KV {kv_bytes / 1e6:.0f} MB  {kv_bytes / dt / 1e12:.2f} TB/s"
     )
