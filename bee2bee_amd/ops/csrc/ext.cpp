@@ -9,6 +9,8 @@
 
 #include <climits>
 
+#include "attn_decode.h"
+
 using torch::Tensor;
 
 extern "C" {
@@ -40,12 +42,6 @@ void launch_kv_store_fp8(const unsigned short*, const unsigned short*,
                          long, hipStream_t);
 void launch_swiglu(const unsigned short*, unsigned short*, long, long,
                    hipStream_t);
-void launch_attn_decode(const unsigned short*, const void*, const void*,
-                        const int*, const int*, unsigned short*, float*,
-                        float*, unsigned short*, float*, int, int, int, int,
-                        int, int, int, long, float, int, const float*,
-                        const float*, int, int, int, hipStream_t);
-void attn_decode_plan(int, int, int, int, int, int, int, int*, int*);
 void launch_attn_prefill(const unsigned short*, const unsigned short*,
                          const unsigned short*, const int*, unsigned short*,
                          int, int, int, int, long, long, long, int, float,
@@ -325,9 +321,9 @@ std::vector<Tensor> attn_decode_impl(const Tensor& q, const Tensor& k_cache,
     TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == hd);
     Tensor out = torch::empty({B, nq, hd}, q.options());
     // flash-decoding split: one partial per 256-key chunk, then combine
-    const int kDecChunk = 256;  // keep in sync with DEC_CHUNK
-    const int C = (W * bs + kDecChunk - 1) / kDecChunk;
-    TORCH_CHECK(C <= 128, "decode supports up to 32768-token contexts for now");
+    const int C = (W * bs + DEC_CHUNK - 1) / DEC_CHUNK;
+    TORCH_CHECK(C <= DEC_MAX_CHUNKS,
+                "decode supports up to 32768-token contexts for now");
     TORCH_CHECK(path != 2 || hd == 64 || hd == 128,
                 "attn_decode: the fused kernel supports head_dim 64 and 128, "
                 "got ", hd);
@@ -338,7 +334,7 @@ std::vector<Tensor> attn_decode_impl(const Tensor& q, const Tensor& k_cache,
     // the fused kernel keeps p in LDS, and with Z == 1 (FOLD) writes out
     // directly: no scratch at all
     Tensor p_buf, part_o, part_ml;
-    if (!fused) p_buf = torch::empty({B, nkv, C, kDecChunk, G}, q.options());
+    if (!fused) p_buf = torch::empty({B, nkv, C, DEC_CHUNK, G}, q.options());
     if (!fused || Z > 1) {
         part_o = torch::empty({B, nkv, C, G, hd}, fopt);
         part_ml = torch::empty({B, nkv, C, G, 2}, fopt);

@@ -25,8 +25,8 @@
 //   the register-direct variant measured 13.8% LDSBankConflict cycles).
 //   Loads prefetch TWO K-groups ahead with SET/BUF as literals so the
 //   compiler tracks exactly which outstanding loads each LDS write waits
-//   on (a runtime-indexed set forced vmcnt(0): measured 2x slower in
-//   attn_pv_mfma_kernel, attn_decode.hip).
+//   on (a runtime-indexed set forced vmcnt(0): measured 2x slower in the
+//   MFMA PV experiment of attn_decode.hip, docs/KERNELS.md).
 //   Experts with more rows loop in 128-row passes (W re-read per pass —
 //   at M>=128/pass the arithmetic intensity is past the memory knee).
 //
