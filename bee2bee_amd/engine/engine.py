@@ -24,7 +24,7 @@ from ..models.spec import ModelSpec, resolve_spec
 from ..models.tokenizer import load_tokenizer
 from ..models.weights import ModelWeights
 from ..utils import new_id, report_engine_throughput
-from .graphs import DecodeGraphs, decode_slot_mapping
+from .graphs import DecodeGraphs, DecodeState
 from .kv import PagedKV
 from . import kv as kv_mod
 from .runner import Runner
@@ -243,6 +243,14 @@ class GenerationRequest:
     on_emit: Optional[Any] = None
 
 
+def _penalize(logits: torch.Tensor, seen: torch.Tensor, p) -> torch.Tensor:
+    """Repetition penalty over a seen-token mask: seen logits are divided
+    by p when positive, multiplied when not. p: a float, or one per row
+    as [rows, 1]."""
+    return torch.where(
+        seen, torch.where(logits > 0, logits / p, logits * p), logits)
+
+
 class _Active:
     __slots__ = ("req", "seq_id", "length", "prefilled", "spec_index",
                  "pen_slot")
@@ -402,6 +410,9 @@ class InferenceEngine:
         self._scratch_seq = -1
         self.kv.new_seq(self._scratch_seq)
         self.kv.extend_seq(self._scratch_seq, 1)
+        # the decode inputs on the device, serving and benchmark alike
+        self._decode = DecodeState(self.runner, self.graphs,
+                                   self._scratch_seq)
 
         self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(seed)
@@ -414,6 +425,7 @@ class InferenceEngine:
         # penalty-1.0-only workloads (bench).
         self._pen_pool: Optional[torch.Tensor] = None
         self._pen_free: List[int] = []
+        self._pen_slot_cache: Optional[tuple] = None  # (slots, tensor)
 
         self._busy_s = 0.0       # engine-thread time inside working steps
         self._busy_steps = 0
@@ -424,9 +436,6 @@ class InferenceEngine:
         # they prefill one chunk per step (vs the paged history) while the
         # active set keeps decoding — chunked prefill
         self._prefilling: List[_Active] = []
-        self._dec_seqs = None  # device-state cache key (active seq ids)
-        self._last_sampled: Optional[torch.Tensor] = None
-        self._eager_state = None
         self._next_seq = 0
         self._stop = False
         self._wake = threading.Event()
@@ -795,43 +804,15 @@ class InferenceEngine:
         # _active and _prefilling) instead of orphaning admitted requests
         self._prefilling = list(queue_)
 
-        dev = self.device
-        ids_list, pos_list, slot_list, cu = [], [], [], [0]
-        for a, start, take in batch:
-            p = a.req.prompt_ids
-            self.kv.extend_seq(a.seq_id, start + take)
-            a.prefilled = a.length = start + take
-            ids_list.extend(p[start : start + take])
-            pos_list.extend(range(start, start + take))
-            slot_list.extend(
-                self.kv.slot_mapping(a.seq_id, range(start, start + take))
-            )
-            cu.append(cu[-1] + take)
-        input_ids = torch.tensor(ids_list, dtype=torch.int64).to(dev, non_blocking=True)
-        positions = torch.tensor(pos_list, dtype=torch.int32).to(dev, non_blocking=True)
-        slots = torch.tensor(slot_list, dtype=torch.int32).to(dev, non_blocking=True)
-        cu_seqlens = torch.tensor(cu, dtype=torch.int32).to(dev, non_blocking=True)
-        max_len = max(take for _, _, take in batch)
         whole = all(
             start == 0 and take == len(a.req.prompt_ids)
             for a, start, take in batch
         )
-        if whole:
-            hidden = self.runner.forward_prefill(
-                input_ids, positions, slots, cu_seqlens, max_len
-            )
-        else:
-            bt = self.kv.block_table([a.seq_id for a, _, _ in batch])
-            seq_lens = torch.tensor([start + take for _, start, take in batch],
-                dtype=torch.int32, device=dev,
-            )
-            query_lens = torch.tensor(
-                [take for _, _, take in batch], dtype=torch.int32).to(dev, non_blocking=True)
-            hidden = self.runner.forward_prefill(
-                input_ids, positions, slots, cu_seqlens, max_len,
-                block_table=bt, seq_lens=seq_lens, query_lens=query_lens,
-            )
-        for a, _, _ in batch:  # the chunk is committed
+        hidden, cu = self._forward_packed(
+            [(a, start, a.req.prompt_ids[start : start + take])
+             for a, start, take in batch], paged=not whole)
+        for a, start, take in batch:  # the chunk is committed
+            a.prefilled = a.length = start + take
             self._release_window(a)
         self._prefilling = [
             a
@@ -847,28 +828,70 @@ class InferenceEngine:
         if not done_idx:
             return
         completed = [batch[i][0] for i in done_idx]
-        last_rows = torch.tensor([cu[i + 1] - 1 for i in done_idx], dtype=torch.int64).to(dev, non_blocking=True)
+        last_rows = self._dev([cu[i + 1] - 1 for i in done_idx], torch.int64)
         logits = self.runner.lm_head(hidden[last_rows])
-        self._sample_and_emit(completed, logits, update_last=False)
-        for a in completed:
-            if a.req.done_ts is not None:
-                # finished AT prefill (max_new=1 / instant stop token):
-                # retire here or the KV blocks leak until shutdown
-                self.kv.free_seq(a.seq_id)
-                self._pen_release(a)
-            else:
-                self._active.append(a)
+        self._sample_and_emit(completed, logits)
+        # a request can finish AT prefill (max_new=1 / instant stop token):
+        # retire it here or its KV blocks leak until shutdown
+        self._active.extend(self._retire(completed))
+
+    def _dev(self, values: Sequence[int], dtype: torch.dtype) -> torch.Tensor:
+        """Host list -> device tensor, without the synchronizing pageable
+        copy of torch.tensor(..., device=cuda)."""
+        return torch.tensor(values, dtype=dtype).to(self.device,
+                                                    non_blocking=True)
+
+    def _forward_packed(self, items: List[tuple], paged: bool):
+        """Grow each sequence by its tokens and run them as one packed
+        varlen batch. items: (active, start, tokens), the tokens sitting at
+        positions start.. of the sequence. paged=True attends each
+        sequence's paged history below `start` as well (chunked prefill,
+        speculative verify). Returns (hidden [T, H], cu host list)."""
+        ids_list, pos_list, slot_list, cu = [], [], [], [0]
+        for a, start, toks in items:
+            span = range(start, start + len(toks))
+            self.kv.extend_seq(a.seq_id, span.stop)
+            ids_list.extend(toks)
+            pos_list.extend(span)
+            slot_list.extend(self.kv.slot_mapping(a.seq_id, span))
+            cu.append(cu[-1] + len(toks))
+        qlens = [len(toks) for _, _, toks in items]
+        args = (self._dev(ids_list, torch.int64),
+                self._dev(pos_list, torch.int32),
+                self._dev(slot_list, torch.int32),
+                self._dev(cu, torch.int32), max(qlens))
+        if not paged:
+            return self.runner.forward_prefill(*args), cu
+        bt = self.kv.block_table([a.seq_id for a, _, _ in items])
+        seq_lens = torch.tensor(
+            [start + q for (_, start, _), q in zip(items, qlens)],
+            dtype=torch.int32, device=self.device)
+        hidden = self.runner.forward_prefill(
+            *args, block_table=bt, seq_lens=seq_lens,
+            query_lens=self._dev(qlens, torch.int32))
+        return hidden, cu
+
+    def _retire(self, acts: List[_Active]) -> List[_Active]:
+        """Free the KV pages and penalty rows of the finished requests in
+        `acts`; returns the ones still running."""
+        done = [a for a in acts if a.req.done_ts is not None]
+        if not done:
+            return acts
+        for a in done:
+            self.kv.free_seq(a.seq_id)
+            self._pen_release(a)
+        return [a for a in acts if a.req.done_ts is None]
 
     @torch.no_grad()
     def _decode_once(self) -> None:
         """One decode step over the active set.
 
-        Host work is incremental: the device-side ids/positions/lens/block
-        tables persist across steps and are bumped in place; full rebuilds
-        happen only when the active set changes membership or a sequence
-        crosses a KV-block boundary (every block_size tokens)."""
-        B = len(self._active)
-        dev = self.device
+        Host work is incremental: the decode state's device-side inputs
+        persist across steps and are bumped in place; full rebuilds happen
+        only when the active set changed membership or was stepped by
+        another path (speculative verify), and block tables are re-read
+        only when a sequence crosses a KV-block boundary (every block_size
+        tokens) or releases a window page."""
         # pages released below the window since the last step: their table
         # entries now read 0
         blocks_changed = self._window_released
@@ -880,86 +903,25 @@ class InferenceEngine:
             blocks_changed |= nblk1 != nblk0
 
         seqs = [a.seq_id for a in self._active]
-        stable = (
-            seqs == self._dec_seqs
-            and self._last_sampled is not None
-            and self._last_sampled.shape[0] >= B
-        )
-
-        if self.graphs is not None:
-            g = self.graphs
-            bucket = g.bucket_for(B)
-            if stable:
-                g.input_ids[:B].copy_(self._last_sampled[:B])
-                g.positions[:B].add_(1)
-                g.seq_lens[:B].add_(1)
-                if blocks_changed:
-                    bt = self.kv.block_table(seqs)
-                    g.block_table[:B, : bt.shape[1]].copy_(bt, non_blocking=True)
-            else:
-                last_ids = [
-                    (a.req.output_ids[-1] if a.req.output_ids else a.req.prompt_ids[-1])
-                    for a in self._active
-                ]
-                g.input_ids[:B].copy_(
-                    torch.tensor(last_ids, dtype=torch.int64), non_blocking=True
-                )
-                g.positions[:B].copy_(
-                    torch.tensor([a.length for a in self._active],
-                                 dtype=torch.int32), non_blocking=True
-                )
-                g.seq_lens[:B].copy_(
-                    torch.tensor([a.length + 1 for a in self._active],
-                                 dtype=torch.int32), non_blocking=True
-                )
-                bt = self.kv.block_table(seqs)
-                g.block_table[:B, : bt.shape[1]].copy_(bt, non_blocking=True)
-                if bucket > B:  # pad rows -> scratch sequence, length 1
-                    sb = self.kv.block_table([self._scratch_seq])[0]
-                    g.block_table[B:bucket, : sb.shape[0]].copy_(sb)
-                    g.positions[B:bucket].zero_()
-                    g.seq_lens[B:bucket].fill_(1)
-                    g.input_ids[B:bucket].zero_()
-                self._dec_seqs = list(seqs)
-            logits = g.run(B)[:B]
+        st = self._decode
+        next_ids = st.pending(seqs)
+        if next_ids is not None:
+            st.advance(next_ids, blocks_changed)
         else:
-            st = self._eager_state
-            if stable and st is not None:
-                st["ids"].copy_(self._last_sampled[:B])
-                st["pos"].add_(1)
-                st["lens"].add_(1)
-                if blocks_changed:
-                    st["bt"] = self.kv.block_table(seqs)
-            else:
-                last_ids = [
-                    (a.req.output_ids[-1] if a.req.output_ids else a.req.prompt_ids[-1])
-                    for a in self._active
-                ]
-                st = {
-                    "ids": torch.tensor(last_ids, dtype=torch.int64).to(dev, non_blocking=True),
-                    "pos": torch.tensor([a.length for a in self._active], dtype=torch.int32).to(dev, non_blocking=True),
-                    "lens": torch.tensor([a.length + 1 for a in self._active], dtype=torch.int32).to(dev, non_blocking=True),
-                    "bt": self.kv.block_table(seqs),
-                }
-                self._eager_state = st
-                self._dec_seqs = list(seqs)
-            slots = decode_slot_mapping(st["bt"], st["pos"], self.kv.block_size)
-            hidden = self.runner.forward_decode(
-                st["ids"], st["pos"], slots, st["bt"], st["lens"]
-            )
-            logits = self.runner.lm_head(hidden)
+            st.load(seqs,
+                    [(a.req.output_ids or a.req.prompt_ids)[-1]
+                     for a in self._active],
+                    [a.length for a in self._active])
+        logits = st.logits()
 
         for a in self._active:
             a.length += 1
             self._release_window(a)
-        self._sample_and_emit(self._active, logits)
-        done = [a for a in self._active if a.req.done_ts is not None]
-        for a in done:
-            self.kv.free_seq(a.seq_id)
-            self._pen_release(a)
-        if done:
-            self._active = [a for a in self._active if a.req.done_ts is None]
-            self._dec_seqs = None  # membership changed
+        # only this step hands ids to the decode state: ids sampled for any
+        # other batch (prefill completions, speculative subsets) would feed
+        # these sequences their neighbours' tokens
+        st.hold(seqs, self._sample_and_emit(self._active, logits))
+        self._active = self._retire(self._active)
 
     # ------------------------------------------------- speculative decoding
 
@@ -970,7 +932,7 @@ class InferenceEngine:
         naive scan; n sizes tried {spec_ngram+2, spec_ngram+1, spec_ngram}."""
         if k <= 0:
             return []
-        idx = getattr(a, "spec_index", None)
+        idx = a.spec_index
         if idx is None:
             from .spec import NGramIndex
 
@@ -987,12 +949,25 @@ class InferenceEngine:
         token plus up to spec_k proposed tokens in ONE forward through the
         chunked-prefill (paged-history) path; the accepted prefix is exactly
         what plain greedy decode would emit (verification is exact)."""
-        dev = self.device
         acts = self._active
         # propose first: when nothing is speculatable this step, take the
         # plain (hipGraph-captured) decode path instead of the slower
         # verify-forward — spec mode then costs ~nothing on workloads
         # without self-similarity
+        props = self._spec_propose(acts)
+        if not any(props):
+            self.spec_stats["delegated"] += 1
+            self._decode_once()
+            return
+        logits, cu = self._spec_verify(acts, props)
+        self._spec_accept(acts, props, logits, cu)
+        self.spec_stats["steps"] += 1
+        # the sequences moved on without the decode state
+        self._decode.forget()
+        self._active = self._retire(acts)
+
+    def _spec_propose(self, acts: List[_Active]) -> List[List[int]]:
+        """Up to spec_k proposed tokens per sequence ([] = none)."""
         props: List[List[int]] = []
         for a in acts:
             r = a.req
@@ -1008,38 +983,21 @@ class InferenceEngine:
                 kcap = min(self.spec_k, room, rem)
                 prop = self._propose(a, r.prompt_ids + r.output_ids, kcap)
             props.append(prop)
-        if not any(props):
-            self.spec_stats["delegated"] += 1
-            self._decode_once()
-            return
-        ids_list, pos_list, slot_list, cu = [], [], [], [0]
-        for a, prop in zip(acts, props):
-            r = a.req
-            ctx = r.prompt_ids + r.output_ids
-            toks = [ctx[-1]] + prop
-            self.kv.extend_seq(a.seq_id, a.length + len(toks))
-            ids_list.extend(toks)
-            pos_list.extend(range(a.length, a.length + len(toks)))
-            slot_list.extend(
-                self.kv.slot_mapping(a.seq_id, range(a.length, a.length + len(toks)))
-            )
-            cu.append(cu[-1] + len(toks))
-        input_ids = torch.tensor(ids_list, dtype=torch.int64).to(dev, non_blocking=True)
-        positions = torch.tensor(pos_list, dtype=torch.int32).to(dev, non_blocking=True)
-        slots = torch.tensor(slot_list, dtype=torch.int32).to(dev, non_blocking=True)
-        cu_t = torch.tensor(cu, dtype=torch.int32).to(dev, non_blocking=True)
-        qlens = [cu[i + 1] - cu[i] for i in range(len(acts))]
-        bt = self.kv.block_table([a.seq_id for a in acts])
-        seq_lens = torch.tensor([a.length + q for a, q in zip(acts, qlens)],
-            dtype=torch.int32, device=dev,
-        )
-        qlens_t = torch.tensor(qlens, dtype=torch.int32).to(dev, non_blocking=True)
-        hidden = self.runner.forward_prefill(
-            input_ids, positions, slots, cu_t, max(qlens),
-            block_table=bt, seq_lens=seq_lens, query_lens=qlens_t,
-        )
-        logits = self.runner.lm_head(hidden)
+        return props
 
+    def _spec_verify(self, acts: List[_Active], props: List[List[int]]):
+        """One forward over every sequence's pending token plus its
+        proposal, against the paged history: logits for all verify rows,
+        and the host list of row offsets per sequence."""
+        hidden, cu = self._forward_packed(
+            [(a, a.length, [(a.req.output_ids or a.req.prompt_ids)[-1]] + prop)
+             for a, prop in zip(acts, props)], paged=True)
+        return self.runner.lm_head(hidden), cu
+
+    def _spec_accept(self, acts: List[_Active], props: List[List[int]],
+                     logits: torch.Tensor, cu: List[int]) -> None:
+        """Emit, per sequence, the longest verified prefix of its proposal
+        plus the one token the model gives after it."""
         greedy_idx = [i for i, a in enumerate(acts)
                       if a.req.sampling.greedy
                       and a.req.sampling.repetition_penalty == 1.0]
@@ -1062,14 +1020,12 @@ class InferenceEngine:
                 row_ids.extend(range(cu[i], cu[i] + q))
                 row_act.extend([i] * q)
                 row_p.extend([acts[i].req.sampling.repetition_penalty] * q)
-            rid = torch.tensor(row_ids, dtype=torch.int64).to(dev, non_blocking=True)
-            slot_t = torch.tensor([acts[i].pen_slot for i in row_act], dtype=torch.int64).to(dev, non_blocking=True)
-            p_t = torch.tensor(row_p, dtype=torch.float32).to(dev, non_blocking=True).unsqueeze(1)
-            gl = logits[rid].float()
-            seen = self._pen_pool[slot_t]
-            pen_rows = torch.where(
-                seen, torch.where(gl > 0, gl / p_t, gl * p_t), gl)
-            pa = pen_rows.argmax(dim=-1).cpu()
+            rid = self._dev(row_ids, torch.int64)
+            slot_t = self._dev([acts[i].pen_slot for i in row_act],
+                               torch.int64)
+            p_t = self._dev(row_p, torch.float32).unsqueeze(1)
+            pa = _penalize(logits[rid].float(), self._pen_pool[slot_t],
+                           p_t).argmax(dim=-1).cpu()
             for k, row in enumerate(row_ids):
                 pen_argmax[row] = int(pa[k])
         now = time.time()
@@ -1119,59 +1075,31 @@ class InferenceEngine:
             for tok in emitted:
                 if r.done_ts is not None:
                     break
-                if r.first_token_ts is None:
-                    r.first_token_ts = now
-                r.output_ids.append(tok)
                 if a.pen_slot is not None:
                     pen_new_slots.append(a.pen_slot)
                     pen_new_toks.append(tok)
                 n_emitted += 1
-                done = (r.cancelled or tok in r.stop_token_ids
-                        or len(r.output_ids) >= r.max_new_tokens)
-                if done:
-                    r.done_ts = now
-                if r.on_emit is not None:
-                    try:
-                        r.on_emit(tok, done)
-                    except Exception:
-                        logger.exception("on_emit callback failed")
-                else:
-                    r.out_queue.put(tok)
-                    if done:
-                        r.out_queue.put(_STREAM_END)
+                self._emit(a, tok, now)
         if n_emitted:
             self._note_throughput(n_emitted, now)
         # mark penalized-greedy emissions seen (one batched scatter)
         if pen_new_slots:
-            self._pen_pool[
-                torch.tensor(pen_new_slots, dtype=torch.int64).to(dev, non_blocking=True),
-                torch.tensor(pen_new_toks, dtype=torch.int64).to(dev, non_blocking=True),
-            ] = True
+            self._pen_pool[self._dev(pen_new_slots, torch.int64),
+                           self._dev(pen_new_toks, torch.int64)] = True
         if nong:
             # non-greedy requests take the plain one-token path
-            rows = torch.tensor(
-                [cu[i + 1] - 1 for i, a in enumerate(acts)
-                 if i not in handled],
-                dtype=torch.int64,
-            ).to(logits.device, non_blocking=True)
+            rows = self._dev([cu[i + 1] - 1 for i in range(len(acts))
+                              if i not in handled], torch.int64)
             for a in nong:
                 a.length += 1
                 self._release_window(a)
-            self._sample_and_emit(nong, logits[rows], update_last=False)
-        self.spec_stats["steps"] += 1
-        self._dec_seqs = None  # device decode-state caches are stale
-        done_acts = [a for a in acts if a.req.done_ts is not None]
-        for a in done_acts:
-            self.kv.free_seq(a.seq_id)
-            self._pen_release(a)
-        if done_acts:
-            self._active = [a for a in acts if a.req.done_ts is None]
+            self._sample_and_emit(nong, logits[rows])
 
     def _pen_slots_t(self, slots: List[int]) -> torch.Tensor:
         """Device tensor of pen-pool slots, cached against the slot list
         (the active set changes far less often than it steps)."""
         key = tuple(slots)
-        cached = getattr(self, "_pen_slot_cache", None)
+        cached = self._pen_slot_cache
         if cached is not None and cached[0] == key:
             return cached[1]
         t = torch.tensor(slots, dtype=torch.int64, device=self.device)
@@ -1201,8 +1129,32 @@ class InferenceEngine:
             self._pen_free.append(a.pen_slot)
             a.pen_slot = None
 
-    def _sample_and_emit(self, acts: List[_Active], logits: torch.Tensor,
-                         update_last: bool = True) -> None:
+    def _emit(self, a: _Active, tok: int, now: float) -> bool:
+        """Record one token of a request and hand it to its consumer;
+        returns whether the request is done with it."""
+        r = a.req
+        if r.first_token_ts is None:
+            r.first_token_ts = now
+        r.output_ids.append(tok)
+        done = (r.cancelled or tok in r.stop_token_ids
+                or len(r.output_ids) >= r.max_new_tokens)
+        if done:
+            r.done_ts = now
+        if r.on_emit is not None:
+            try:
+                r.on_emit(tok, done)
+            except Exception:
+                logger.exception("on_emit callback failed")
+        else:
+            r.out_queue.put(tok)
+            if done:
+                r.out_queue.put(_STREAM_END)
+        return done
+
+    def _sample_and_emit(self, acts: List[_Active],
+                         logits: torch.Tensor) -> torch.Tensor:
+        """Sample one token per row of logits [len(acts), V] and emit it;
+        returns the sampled ids on the device."""
         # group rows by sampling params so each group is one sample() call
         groups: Dict[tuple, List[int]] = {}
         for i, a in enumerate(acts):
@@ -1235,11 +1187,10 @@ class InferenceEngine:
                 slots = [acts[r].pen_slot for r in rows]
                 if self._pen_pool is not None and all(
                         sl is not None for sl in slots):
-                    seen = self._pen_pool[self._pen_slots_t(slots)]
-                    p = sp.repetition_penalty
-                    gl = grp_logits.float()
-                    grp_logits = torch.where(
-                        seen, torch.where(gl > 0, gl / p, gl * p), gl)
+                    grp_logits = _penalize(
+                        grp_logits.float(),
+                        self._pen_pool[self._pen_slots_t(slots)],
+                        sp.repetition_penalty)
                 else:
                     # pool exhausted fallback: host-rebuilt history
                     from .sampler import apply_repetition_penalty
@@ -1276,39 +1227,12 @@ class InferenceEngine:
                 idx_t = torch.tensor(pen_idx, dtype=torch.int64,
                                      device=logits.device)
                 self._pen_pool[slot_t, next_dev[idx_t]] = True
-        if update_last:
-            # feeds the next decode step without an H2D copy. Callers whose
-            # `acts` is NOT the current decode set (prefill completions,
-            # spec-decode subsets) must pass update_last=False: the decode
-            # stable-path copies _last_sampled[:B] as the next inputs, and a
-            # clobber from another batch feeds WRONG TOKENS (a request once
-            # decoded its neighbor's token — caught by the scheduling-
-            # invariance property test).
-            self._last_sampled = next_dev
         next_ids = next_dev.cpu()  # the one host sync per step (emission)
         now = time.time()
-        n_emitted = 0
         for i, a in enumerate(acts):
-            tok = int(next_ids[i])
-            r = a.req
-            if r.first_token_ts is None:
-                r.first_token_ts = now
-            r.output_ids.append(tok)
-            n_emitted += 1
-            done = (r.cancelled or tok in r.stop_token_ids
-                    or len(r.output_ids) >= r.max_new_tokens)
-            if done:
-                r.done_ts = now
-            if r.on_emit is not None:
-                try:
-                    r.on_emit(tok, done)
-                except Exception:
-                    logger.exception("on_emit callback failed")
-            else:
-                r.out_queue.put(tok)
-                if done:
-                    r.out_queue.put(_STREAM_END)
-        self._note_throughput(n_emitted, now)
+            self._emit(a, int(next_ids[i]), now)
+        self._note_throughput(len(acts), now)
+        return next_dev
 
     def stats(self) -> Dict[str, Any]:
         """Live engine observability (served at the API home endpoint)."""
@@ -1432,69 +1356,24 @@ class InferenceEngine:
                                      distinct=distinct)
         for sid in seq_ids:
             self.kv.extend_seq(sid, prompt_len + steps_budget + 1)
-        dev = self.device
-        acts = self._bench_acts
-        first = torch.tensor([a.req.output_ids[-1] for a in acts], dtype=torch.int64).to(dev, non_blocking=True)
-        bt = self.kv.block_table([a.seq_id for a in acts])
+        self._decode.load(seq_ids,
+                          [a.req.output_ids[-1] for a in self._bench_acts],
+                          [prompt_len] * batch)
         if self.graphs is not None:
-            g = self.graphs
-            assert g.bucket_for(batch) == batch or batch in g.buckets(), (
-                "bench batch should be a graph bucket"
-            )
-            g.input_ids[:batch].copy_(first)
-            g.positions[:batch].fill_(prompt_len)
-            g.seq_lens[:batch].fill_(prompt_len + 1)
-            g.block_table[:batch, : bt.shape[1]].copy_(bt)
-            bucket = g.bucket_for(batch)
-            if bucket > batch:
-                sb = self.kv.block_table([self._scratch_seq])[0]
-                g.block_table[batch:bucket, : sb.shape[0]].copy_(sb)
-                g.positions[batch:bucket].zero_()
-                g.seq_lens[batch:bucket].fill_(1)
-                g.input_ids[batch:bucket].zero_()
-            self._bench_state = ("graph", batch)
-            self.graphs.run(batch)  # capture outside the timed region
-            g.positions[:batch].fill_(prompt_len)
-            g.seq_lens[:batch].fill_(prompt_len + 1)
-            g.input_ids[:batch].copy_(first)
-        else:
-            self._bench_eager = {
-                "ids": first.clone(),
-                "pos": torch.full((batch,), prompt_len, dtype=torch.int32, device=dev),
-                "lens": torch.full((batch,), prompt_len + 1, dtype=torch.int32, device=dev),
-                "bt": bt,
-            }
-            self._bench_state = ("eager", batch)
+            # capture outside the timed region (the run only reads the
+            # decode inputs, and rewrites the same KV slot at prompt_len)
+            self._decode.logits()
+        self._bench_state = (
+            "graph" if self.graphs is not None else "eager", batch)
+
+    @property
+    def _bench_eager(self) -> Dict[str, torch.Tensor]:
+        """What the benchmark's output dump reads on the eager backend."""
+        return {"ids": self._decode.ids}
 
     @torch.no_grad()
     def bench_step(self) -> None:
         """One fully device-side greedy decode step over the bench batch."""
-        mode, B = self._bench_state
-        if mode == "graph":
-            g = self.graphs
-            logits = g.run(B)[:B]
-            next_ids = torch.argmax(logits, dim=-1)
-            g.input_ids[:B].copy_(next_ids)
-            g.positions[:B].add_(1)
-            g.seq_lens[:B].add_(1)
-        else:
-            st = self._bench_eager
-            slots = decode_slot_mapping(st["bt"], st["pos"], self.kv.block_size)
-            hidden = self.runner.forward_decode(
-                st["ids"], st["pos"], slots, st["bt"], st["lens"]
-            )
-            logits = self.runner.lm_head(hidden)
-            st["ids"].copy_(torch.argmax(logits, dim=-1))
-            st["pos"].add_(1)
-            st["lens"].add_(1)
-        self.total_tokens += B
-
-    @torch.no_grad()
-    def bench_decode_step(self) -> torch.Tensor:
-        """One decode step over the bench batch; returns sampled ids [B]."""
-        acts = self._bench_acts
-        saved = self._active
-        self._active = list(acts)
-        self._decode_once()
-        self._active = saved
-        return torch.tensor([a.req.output_ids[-1] for a in acts])
+        st = self._decode
+        st.advance(torch.argmax(st.logits(), dim=-1), False)
+        self.total_tokens += self._bench_state[1]

@@ -1,11 +1,28 @@
-"""hipGraph-captured decode steps.
+"""The decode step's device inputs and its hipGraph-captured replay.
 
-The decode step is a chain of ~100 small kernel launches per layer-stack
-pass; at batch<32 launch overhead is a visible fraction of the step. We
-capture the whole step (embed → layers → lm_head → slot math) per batch-size
-bucket with torch.cuda.CUDAGraph (hipGraph on ROCm) into static buffers and
-replay it. Buffers are updated in-place with device ops between replays —
-no host sync in the loop.
+One decode step reads four device tensors, one row per sequence:
+
+    ids        int64 [B]     token fed to the step (the last one sampled)
+    positions  int32 [B]     its position, i.e. tokens already in the cache
+    seq_lens   int32 [B]     positions + 1
+    block_table int32 [B, W] KV pages of each sequence
+
+`DecodeState` is their only writer. `load()` rebuilds them from host
+lists, `advance()` bumps them in place with device ops, `logits()` runs the
+step. The engine's serving step and its benchmark step are both callers of
+those three and hold no copy of the inputs themselves.
+
+With `DecodeGraphs` the four tensors are views of its static buffers
+[max_batch(, width)], whose storage never moves: the captured graphs hold
+the pointers. The decode step is a chain of ~100 small kernel launches per
+layer-stack pass; at batch<32 launch overhead is a visible fraction of the
+step, so the whole step (embed → layers → lm_head → slot math) is captured
+per batch-size bucket with torch.cuda.CUDAGraph (hipGraph on ROCm) and
+replayed. A replay runs `bucket` rows: `load()` points rows [B:bucket] at
+the scratch sequence, and nothing writes them afterwards. Without graphs
+the tensors are fresh per `load()`, and the block table is the narrow one
+`kv.block_table` returns: the attention binding sizes its chunk count, and
+so its kernel plan, from that width.
 
 Capture constraints honored: the paged-KV pool is preallocated (kv.py), all
 shapes are static per bucket, the HIP kernels allocate nothing and never
@@ -14,7 +31,7 @@ sync, sampling stays outside the graph (RNG).
 from __future__ import annotations
 
 import logging
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Sequence
 
 import torch
 
@@ -94,9 +111,8 @@ class DecodeGraphs:
         logger.info("captured decode graph for batch bucket %d", B)
 
     def run(self, batch: int) -> torch.Tensor:
-        """Replay (capturing on first use) and return logits [bucket, V].
-        Caller must have filled rows [:batch] of the static buffers and
-        padded rows [batch:bucket] with safe scratch values."""
+        """Replay (capturing on first use) and return logits [bucket, V]
+        for the rows DecodeState.load() wrote."""
         B = self.bucket_for(batch)
         if B not in self._graphs:
             self._capture(B)
@@ -105,3 +121,92 @@ class DecodeGraphs:
         # steps would not be bit-identical with the capture step otherwise.
         self._graphs[B].replay()
         return self.logits[B]
+
+
+class DecodeState:
+    """The four decode inputs of one sequence list, and the ids sampled for
+    it: see the module docstring."""
+
+    def __init__(self, runner, graphs: Optional[DecodeGraphs],
+                 scratch_seq: int) -> None:
+        self.runner = runner
+        self.kv = runner.kv
+        self.graphs = graphs
+        self.scratch_seq = scratch_seq
+        self.seqs: Optional[List[int]] = None  # list the rows were loaded for
+        self._pending: Optional[torch.Tensor] = None
+        self.ids = self.pos = self.lens = self.bt = None
+
+    def load(self, seq_ids: Sequence[int], last_ids: Sequence[int],
+             lengths: Sequence[int]) -> None:
+        """Full rebuild from host lists: sequence i feeds last_ids[i] at
+        position lengths[i] (its tokens already in the cache)."""
+        B, g = len(seq_ids), self.graphs
+        pos = torch.tensor(lengths, dtype=torch.int32)
+        bt = self.kv.block_table(seq_ids)
+        if g is None:
+            dev = self.runner.device
+            self.ids = torch.empty(B, dtype=torch.int64, device=dev)
+            self.pos = torch.empty(B, dtype=torch.int32, device=dev)
+            self.lens = torch.empty(B, dtype=torch.int32, device=dev)
+            self.bt = bt
+        else:
+            self.ids, self.pos, self.lens, self.bt = (
+                g.input_ids[:B], g.positions[:B], g.seq_lens[:B],
+                g.block_table[:B])
+            self.bt[:, : bt.shape[1]].copy_(bt, non_blocking=True)
+            bucket = g.bucket_for(B)
+            if bucket > B:  # pad rows -> scratch sequence, length 1
+                sb = self.kv.block_table([self.scratch_seq])[0]
+                g.block_table[B:bucket, : sb.shape[0]].copy_(sb)
+                g.positions[B:bucket].zero_()
+                g.seq_lens[B:bucket].fill_(1)
+                g.input_ids[B:bucket].zero_()
+        self.ids.copy_(torch.tensor(last_ids, dtype=torch.int64),
+                       non_blocking=True)
+        self.pos.copy_(pos, non_blocking=True)
+        self.lens.copy_(pos + 1, non_blocking=True)
+        self.seqs = list(seq_ids)
+        self._pending = None
+
+    def advance(self, next_ids: torch.Tensor, refresh_tables: bool) -> None:
+        """In-place bump to the next token of the same sequences; device
+        ops only. refresh_tables re-reads the block tables: a sequence
+        crossed a page boundary or released a window page."""
+        self.ids.copy_(next_ids)
+        self.pos.add_(1)
+        self.lens.add_(1)
+        if refresh_tables:
+            bt = self.kv.block_table(self.seqs)
+            if self.graphs is None:
+                self.bt = bt
+            else:
+                self.bt[:, : bt.shape[1]].copy_(bt, non_blocking=True)
+        self._pending = None
+
+    def logits(self) -> torch.Tensor:
+        """Run the step over the loaded rows: logits [B, V]."""
+        if self.graphs is not None:
+            B = len(self.seqs)
+            return self.graphs.run(B)[:B]
+        slots = decode_slot_mapping(self.bt, self.pos, self.kv.block_size)
+        hidden = self.runner.forward_decode(
+            self.ids, self.pos, slots, self.bt, self.lens)
+        return self.runner.lm_head(hidden)
+
+    def hold(self, seq_ids: Sequence[int], next_ids: torch.Tensor) -> None:
+        """Keep next_ids [B], sampled on device for seq_ids, as the next
+        step's inputs (no host round trip). Ids of any other list than the
+        loaded one are not kept: bumping with them fed a request its
+        neighbour's token."""
+        self._pending = next_ids if list(seq_ids) == self.seqs else None
+
+    def pending(self, seq_ids: Sequence[int]) -> Optional[torch.Tensor]:
+        """The held ids if the rows can be bumped for seq_ids, else None
+        (rebuild): the state was loaded for exactly this list and holds
+        ids sampled for it."""
+        return self._pending if list(seq_ids) == self.seqs else None
+
+    def forget(self) -> None:
+        """The sequences moved on without the state: rebuild next time."""
+        self.seqs = self._pending = None

@@ -189,14 +189,15 @@ class PagedKV:
                 - self._seq_released.get(seq_id, 0))
 
     def extend_seq(self, seq_id: int, new_len: int) -> None:
-        """Grow a sequence to new_len tokens, allocating blocks as needed."""
+        """Grow a sequence to new_len tokens, allocating blocks as needed.
+        All or nothing: a request the pool cannot meet takes no block."""
         blocks = self._seq_blocks[seq_id]
         need = (new_len + self.block_size - 1) // self.block_size
+        if need - len(blocks) > len(self._free):
+            raise RuntimeError(
+                f"KV pool exhausted ({self.n_blocks} blocks of {self.block_size})"
+            )
         while len(blocks) < need:
-            if not self._free:
-                raise RuntimeError(
-                    f"KV pool exhausted ({self.n_blocks} blocks of {self.block_size})"
-                )
             blocks.append(self._free.pop())
         self._seq_len[seq_id] = new_len
 

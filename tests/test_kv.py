@@ -44,6 +44,21 @@ def test_pool_exhaustion_raises():
         kv.extend_seq(2, 1)
 
 
+def test_failed_extend_takes_no_block():
+    """A request larger than what is free leaves pool and sequence as they
+    were: block count and length of the sequence still agree."""
+    kv = _pool(3)
+    kv.new_seq(1)
+    kv.extend_seq(1, BLOCK_SIZE)
+    kv.new_seq(2)
+    with pytest.raises(RuntimeError, match="KV pool exhausted"):
+        kv.extend_seq(2, 3 * BLOCK_SIZE)  # needs 3, 2 are free
+    assert kv.free_blocks == 2
+    assert kv.seq_n_blocks(2) == 0 and kv.seq_len(2) == 0
+    kv.extend_seq(2, 2 * BLOCK_SIZE)      # what is free can still be had
+    assert kv.free_blocks == 0
+
+
 def test_slot_mapping_spans_pages():
     kv = _pool(4)
     kv.new_seq(9)
