@@ -105,10 +105,5 @@ __device__ __forceinline__ float wave_sum(float v) {
 #define BB_KASSERT(cond) do { } while (0)
 #endif
 
-#define HIP_CHECK_KERNEL()                                                    \
-    do {                                                                      \
-        hipError_t e_ = hipGetLastError();                                    \
-        if (e_ != hipSuccess)                                                 \
-            TORCH_CHECK(false, "HIP kernel launch failed: ",                  \
-                        hipGetErrorString(e_));                               \
-    } while (0)
+// Launch status is checked by the bindings (ext.cpp check_launch), after
+// every launch_* call: the launchers here stay free of torch headers.

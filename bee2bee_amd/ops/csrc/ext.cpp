@@ -3,6 +3,7 @@
 // Validation lives here (shape/dtype/device checks) so the kernels stay
 // branch-free. All entry points are hipGraph-capture safe: no allocation
 // beyond torch's caching allocator, no synchronization, no host reads.
+// Every launch is followed by check_launch, and an empty grid never launches.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
@@ -110,16 +111,50 @@ void check_bf16(const Tensor& t, const char* name) {
     TORCH_CHECK(t.scalar_type() == torch::kBFloat16, name, " must be bf16");
 }
 
+// Follows every launch: a launch the runtime refuses (too much dynamic LDS,
+// an empty or oversized grid) would otherwise hand back torch::empty memory.
+// hipGetLastError reads and clears a host-side status: no synchronization,
+// legal under stream capture, and never executed by a graph replay.
+void check_launch(const char* what) {
+    const hipError_t e = hipGetLastError();
+    TORCH_CHECK(e == hipSuccess, what, ": HIP kernel launch failed: ",
+                hipGetErrorString(e));
+}
+
+// The row-norm kernels cache one fp32 row in dynamic LDS (H * 4 bytes) next
+// to 64 bytes of static reduction scratch. Returns H after checking it and
+// the [H] bf16 parameter vectors.
+int check_norm_row(const Tensor& x, const char* what,
+                   std::initializer_list<const Tensor*> params) {
+    TORCH_CHECK(x.dim() >= 1, what, ": x needs at least one dimension");
+    const long H = x.size(-1);
+    TORCH_CHECK(H > 0 && H % 8 == 0, what,
+                ": hidden size must be a positive multiple of 8, got ", H);
+    const long lds = (long)at::cuda::getCurrentDeviceProperties()
+                         ->sharedMemPerBlock;
+    const long h_max = (lds - 64) / 4 / 8 * 8;
+    TORCH_CHECK(H <= h_max, what, ": hidden size ", H, " needs ", H * 4 + 64,
+                " bytes of LDS per workgroup; the device limit is ", lds,
+                " bytes (hidden size <= ", h_max, ")");
+    for (const Tensor* p : params) {
+        check_bf16(*p, "norm weight/bias");
+        TORCH_CHECK(p->dim() == 1 && p->size(0) == H && p->is_contiguous(),
+                    what, ": weight and bias must be bf16 [", H,
+                    "] contiguous");
+    }
+    return (int)H;
+}
+
 Tensor rmsnorm(const Tensor& x, const Tensor& w, double eps) {
     check_bf16(x, "x");
-    check_bf16(w, "w");
-    TORCH_CHECK(x.is_contiguous() && w.is_contiguous());
-    const long T = x.numel() / x.size(-1);
-    const int H = x.size(-1);
-    TORCH_CHECK(H % 8 == 0, "hidden size must be a multiple of 8");
+    TORCH_CHECK(x.is_contiguous());
+    const int H = check_norm_row(x, "rmsnorm", {&w});
+    const long T = x.numel() / H;
     Tensor y = torch::empty_like(x);
+    if (T == 0) return y;
     launch_rmsnorm(bf16p(x), bf16p(w), bf16p_mut(y), T, H, (float)eps,
                    stream());
+    check_launch("rmsnorm");
     return y;
 }
 
@@ -127,15 +162,16 @@ std::vector<Tensor> fused_add_rmsnorm(const Tensor& x, const Tensor& resid,
                                       const Tensor& w, double eps) {
     check_bf16(x, "x");
     check_bf16(resid, "resid");
-    TORCH_CHECK(x.is_contiguous() && resid.is_contiguous() && w.is_contiguous());
+    TORCH_CHECK(x.is_contiguous() && resid.is_contiguous());
     TORCH_CHECK(x.sizes() == resid.sizes());
-    const long T = x.numel() / x.size(-1);
-    const int H = x.size(-1);
-    TORCH_CHECK(H % 8 == 0);
+    const int H = check_norm_row(x, "fused_add_rmsnorm", {&w});
+    const long T = x.numel() / H;
     Tensor y = torch::empty_like(x);
     Tensor resid_out = torch::empty_like(x);
+    if (T == 0) return {y, resid_out};
     launch_fused_add_rmsnorm(bf16p(x), bf16p(resid), bf16p(w), bf16p_mut(y),
                              bf16p_mut(resid_out), T, H, (float)eps, stream());
+    check_launch("fused_add_rmsnorm");
     return {y, resid_out};
 }
 
@@ -153,9 +189,11 @@ void rope_inplace(Tensor& q, Tensor& k, const Tensor& pos, const Tensor& cos_t,
     TORCH_CHECK(k.stride(2) == 1 && k.stride(1) == hd);
     TORCH_CHECK(cos_t.size(1) == hd / 2 && cos_t.is_contiguous() &&
                 sin_t.is_contiguous());
+    if (T == 0 || nq + nkv == 0) return;
     launch_rope(bf16p_mut(q), bf16p_mut(k), pos.data_ptr<int>(),
                 cos_t.data_ptr<float>(), sin_t.data_ptr<float>(), T, nq, nkv,
                 hd, q.stride(0), k.stride(0), stream());
+    check_launch("rope");
 }
 
 // Qwen3 per-head q/k RMSNorm + RoPE, in place. Layout contract of
@@ -198,6 +236,7 @@ void qk_norm_rope_inplace(Tensor& q, Tensor& k, const Tensor& pos,
                         cos_t.data_ptr<float>(), sin_t.data_ptr<float>(),
                         bf16p(q_weight), bf16p(k_weight), T, nq, nkv, hd,
                         q.stride(0), k.stride(0), (float)eps, stream());
+    check_launch("qk_norm_rope");
 }
 
 void kv_cache_store(const Tensor& k, const Tensor& v, Tensor& k_cache,
@@ -215,6 +254,7 @@ void kv_cache_store(const Tensor& k, const Tensor& v, Tensor& k_cache,
     TORCH_CHECK(k.stride(2) == 1 && k.stride(1) == hd);
     TORCH_CHECK(v.stride(2) == 1 && v.stride(1) == hd);
     TORCH_CHECK(hd % 2 == 0);
+    if (T == 0 || nkv == 0) return;
     if (k_cache.scalar_type() == torch::kUInt8) {
         // fp8 (OCP e4m3) cache: quantize at store time
         launch_kv_store_fp8(bf16p(k), bf16p(v),
@@ -225,26 +265,27 @@ void kv_cache_store(const Tensor& k, const Tensor& v, Tensor& k_cache,
                             scaled ? v_inv_scale->data_ptr<float>() : nullptr,
                             T, nkv, hd, bs, k.stride(0), v.stride(0),
                             stream());
+        check_launch("kv_cache_store");
         return;
     }
     check_bf16(k_cache, "k_cache");
     launch_kv_store(bf16p(k), bf16p(v), bf16p_mut(k_cache), bf16p_mut(v_cache),
                     slots.data_ptr<int>(), T, nkv, hd, bs, k.stride(0),
                     v.stride(0), stream());
+    check_launch("kv_cache_store");
 }
 
 Tensor layernorm(const Tensor& x, const Tensor& w, const Tensor& b,
                  double eps) {
     check_bf16(x, "x");
-    check_bf16(w, "w");
-    check_bf16(b, "b");
-    TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && b.is_contiguous());
-    const long T = x.numel() / x.size(-1);
-    const int H = x.size(-1);
-    TORCH_CHECK(H % 8 == 0);
+    TORCH_CHECK(x.is_contiguous());
+    const int H = check_norm_row(x, "layernorm", {&w, &b});
+    const long T = x.numel() / H;
     Tensor y = torch::empty_like(x);
+    if (T == 0) return y;
     launch_layernorm(bf16p(x), bf16p(w), bf16p(b), bf16p_mut(y), T, H,
                      (float)eps, stream());
+    check_launch("layernorm");
     return y;
 }
 
@@ -255,14 +296,15 @@ std::vector<Tensor> fused_add_layernorm(const Tensor& x, const Tensor& resid,
     check_bf16(resid, "resid");
     TORCH_CHECK(x.is_contiguous() && resid.is_contiguous());
     TORCH_CHECK(x.sizes() == resid.sizes());
-    const long T = x.numel() / x.size(-1);
-    const int H = x.size(-1);
-    TORCH_CHECK(H % 8 == 0);
+    const int H = check_norm_row(x, "fused_add_layernorm", {&w, &b});
+    const long T = x.numel() / H;
     Tensor y = torch::empty_like(x);
     Tensor resid_out = torch::empty_like(x);
+    if (T == 0) return {y, resid_out};
     launch_fused_add_layernorm(bf16p(x), bf16p(resid), bf16p(w), bf16p(b),
                                bf16p_mut(y), bf16p_mut(resid_out), T, H,
                                (float)eps, stream());
+    check_launch("fused_add_layernorm");
     return {y, resid_out};
 }
 
@@ -271,18 +313,27 @@ Tensor gelu(const Tensor& x) {
     TORCH_CHECK(x.is_contiguous());
     TORCH_CHECK(x.numel() % 8 == 0);
     Tensor y = torch::empty_like(x);
+    if (x.numel() == 0) return y;
     launch_gelu(bf16p(x), bf16p_mut(y), x.numel(), stream());
+    check_launch("gelu");
     return y;
 }
 
 Tensor swiglu(const Tensor& gu) {
     check_bf16(gu, "gate_up");
     TORCH_CHECK(gu.is_contiguous());
+    TORCH_CHECK(gu.dim() >= 1 && gu.size(-1) > 0 && gu.size(-1) % 16 == 0,
+                "swiglu: the last dimension is 2 * I with I a positive "
+                "multiple of 8");
     const long I = gu.size(-1) / 2;
     const long T = gu.numel() / gu.size(-1);
-    TORCH_CHECK(I % 8 == 0);
-    Tensor out = torch::empty({gu.size(0), I}, gu.options());
+    // shaped like the input: [..., 2I] -> [..., I]
+    std::vector<int64_t> shape(gu.sizes().begin(), gu.sizes().end());
+    shape.back() = I;
+    Tensor out = torch::empty(shape, gu.options());
+    if (T == 0) return out;
     launch_swiglu(bf16p(gu), bf16p_mut(out), T, I, stream());
+    check_launch("swiglu");
     return out;
 }
 
@@ -345,6 +396,10 @@ std::vector<Tensor> attn_decode_impl(const Tensor& q, const Tensor& k_cache,
         out_ml = torch::empty({B, nq, 2}, fopt);
         out_ml_p = out_ml.data_ptr<float>();
     }
+    if (B == 0 || nq == 0) {
+        if (want_lse) return {out, out_ml};
+        return {out};
+    }
     launch_attn_decode(bf16p(q), k_cache.data_ptr(), v_cache.data_ptr(),
                        block_table.data_ptr<int>(), seq_lens.data_ptr<int>(),
                        p_buf.defined() ? bf16p_mut(p_buf) : nullptr,
@@ -355,6 +410,7 @@ std::vector<Tensor> attn_decode_impl(const Tensor& q, const Tensor& k_cache,
                        scaled ? k_scale->data_ptr<float>() : nullptr,
                        scaled ? v_scale->data_ptr<float>() : nullptr,
                        (int)window, (int)path, (int)max_z, stream());
+    check_launch("attn_decode");
     if (want_lse) return {out, out_ml};
     return {out};
 }
@@ -413,15 +469,21 @@ Tensor attn_prefill(const Tensor& q, const Tensor& k, const Tensor& v,
     const int nkv = k.size(1);
     const int nseq = cu_seqlens.size(0) - 1;
     TORCH_CHECK(nq % nkv == 0);
+    // head dims other than the MFMA kernel's 64 / 128 take the basic
+    // kernel: one lane per pair of dims, 64 lanes
+    TORCH_CHECK(hd <= 128 && hd % 2 == 0,
+                "attn_prefill: head_dim must be even and <= 128, got ", hd);
     TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == hd);
     TORCH_CHECK(k.stride(2) == 1 && k.stride(1) == hd);
     TORCH_CHECK(v.stride(2) == 1 && v.stride(1) == hd);
     Tensor out = torch::empty({T, nq, hd}, q.options());
+    if (T == 0 || nq == 0 || nseq <= 0 || max_seqlen <= 0) return out;
     launch_attn_prefill(bf16p(q), bf16p(k), bf16p(v),
                         cu_seqlens.data_ptr<int>(), bf16p_mut(out), nseq, nq,
                         nkv, hd, q.stride(0), k.stride(0), v.stride(0),
                         (int)max_seqlen, (float)scale, causal ? 1 : 0,
                         (int)window, stream());
+    check_launch("attn_prefill");
     return out;
 }
 
@@ -447,11 +509,14 @@ Tensor attn_prefill_paged(const Tensor& q, const Tensor& k_cache,
     const int W = block_table.size(1);
     const int nseq = cu_q.size(0) - 1;
     TORCH_CHECK(nq % nkv == 0);
-    TORCH_CHECK(hd % 8 == 0, "paged prefill needs hd % 8 == 0");
+    TORCH_CHECK(hd % 8 == 0 && hd <= 128,
+                "attn_prefill_paged: head_dim must be a multiple of 8 and "
+                "<= 128, got ", hd);
     TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == hd);
     TORCH_CHECK(k_cache.is_contiguous() && v_cache.is_contiguous());
     TORCH_CHECK(block_table.size(0) == nseq && seq_lens.size(0) == nseq);
     Tensor out = torch::empty({T, nq, hd}, q.options());
+    if (T == 0 || nq == 0 || nseq <= 0 || max_qlen <= 0) return out;
     launch_attn_prefill_paged(bf16p(q), k_cache.data_ptr(),
                               v_cache.data_ptr(), cu_q.data_ptr<int>(),
                               block_table.data_ptr<int>(),
@@ -461,6 +526,7 @@ Tensor attn_prefill_paged(const Tensor& q, const Tensor& k_cache,
                               scaled ? k_scale->data_ptr<float>() : nullptr,
                               scaled ? v_scale->data_ptr<float>() : nullptr,
                               (int)window, stream());
+    check_launch("attn_prefill_paged");
     return out;
 }
 
@@ -476,9 +542,11 @@ Tensor grouped_gemm(const Tensor& x, const Tensor& w, const Tensor& offs) {
     TORCH_CHECK(N % 64 == 0, "N must be a multiple of 64");
     TORCH_CHECK(K % 128 == 0, "K must be a multiple of 128");
     Tensor out = torch::empty({S, N}, x.options());
-    if (S > 0)
+    if (S > 0 && E > 0 && N > 0) {
         launch_grouped_gemm(bf16p(x), bf16p(w), offs.data_ptr<int>(),
                             bf16p_mut(out), E, S, N, K, stream());
+        check_launch("grouped_gemm");
+    }
     return out;
 }
 
@@ -492,6 +560,7 @@ Tensor mfma_probe_fp8(const Tensor& A, const Tensor& B) {
     launch_mfma_probe_fp8(A.data_ptr<unsigned char>(),
                           B.data_ptr<unsigned char>(), C.data_ptr<float>(),
                           stream());
+    check_launch("mfma_probe_fp8");
     return C;
 }
 
@@ -504,6 +573,7 @@ Tensor mfma_probe(const Tensor& A, const Tensor& B) {
     Tensor C = torch::empty({16, 16},
                             A.options().dtype(torch::kFloat32));
     launch_mfma_probe(bf16p(A), bf16p(B), C.data_ptr<float>(), stream());
+    check_launch("mfma_probe");
     return C;
 }
 
@@ -514,6 +584,7 @@ void bw_probe_paged(const Tensor& pool, const Tensor& table, int64_t hd,
     launch_bw_paged(bf16p(pool), table.data_ptr<int>(), pool.numel() / hd,
                     (int)hd, (int)rows_per_page, sink.data_ptr<float>(),
                     stream());
+    check_launch("bw_probe_paged");
 }
 
 void bw_probe(const Tensor& pool, int64_t mode, int64_t hd, int64_t arg) {
@@ -528,6 +599,7 @@ void bw_probe(const Tensor& pool, int64_t mode, int64_t hd, int64_t arg) {
     else
         launch_bw_rowperinstr(bf16p(pool), n / hd, hd, (int)arg,
                               sink.data_ptr<float>(), stream());
+    check_launch("bw_probe");
 }
 
 }  // namespace
