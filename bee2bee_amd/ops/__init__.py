@@ -106,6 +106,12 @@ def rope_inplace(
     cos: torch.Tensor,
     sin: torch.Tensor,
 ) -> None:
+    """Rotate-half RoPE in place on q [T, nq, hd] and k [T, n_kv, hd]
+    (strided views of the fused qkv buffer); positions int32 [T]; cos / sin
+    fp32 [max_len, hd/2]. The HIP binding checks every shape, dtype and
+    device before it launches. It cannot check the VALUES of `positions`
+    without a device sync: 0 <= positions[t] < max_len is the caller's
+    contract, and a position outside it reads past the tables."""
     if _use_hip(q):
         require_hip().rope_inplace(q, k, positions, cos, sin)
         return
@@ -144,7 +150,14 @@ def kv_cache_store(
 ) -> None:
     """k_inv_scale / v_inv_scale: optional fp32 [n_kv_heads] reciprocal
     scales of a scaled fp8 cache (byte = e4m3(clamp(x * inv_scale[h],
-    +-448))). None stores with the fixed unit scale."""
+    +-448))), a NaN input staying a NaN byte. None stores with the fixed
+    unit scale, where |x| > 464 overflows to a NaN byte.
+
+    The HIP binding checks every shape, dtype and device before it
+    launches. It cannot check the VALUES of `slot_mapping` without a device
+    sync: 0 <= slot < n_blocks * block_size is the caller's contract, and a
+    slot outside it writes past the caches. Equal slots in one call race;
+    which row wins is unspecified."""
     if _use_hip(k):
         require_hip().kv_cache_store(k, v, k_cache, v_cache, slot_mapping,
                                      k_inv_scale, v_inv_scale)

@@ -300,8 +300,16 @@ __global__ void kv_store_kernel(
 // instruction's overflow mode; the reciprocal comes from the host, so
 // there is no device-side division. h is wave-uniform (one wave per
 // (token, head)), so the two scales are scalar loads.
+//
+// The clamp is a compare and a select per bound, not fminf / fmaxf: those
+// return the other operand when one is NaN and would store a NaN input as
+// -448 (byte 0xfe), a maximal finite key. Both compares are false for NaN,
+// so it reaches the convert and becomes a NaN byte, as in the reference;
+// +-inf saturate to +-448. Pinned by
+// tests/test_write_path_gpu.py::test_fp8_store_on_every_bf16_pattern[scaled].
 __device__ __forceinline__ float clamp_e4m3(float x) {
-    return fminf(fmaxf(x, -448.f), 448.f);
+    x = x > 448.f ? 448.f : x;
+    return x < -448.f ? -448.f : x;
 }
 
 __global__ void kv_store_fp8_kernel(

@@ -179,16 +179,32 @@ void rope_inplace(Tensor& q, Tensor& k, const Tensor& pos, const Tensor& cos_t,
                   const Tensor& sin_t) {
     check_bf16(q, "q");
     check_bf16(k, "k");
-    TORCH_CHECK(pos.scalar_type() == torch::kInt32);
-    TORCH_CHECK(cos_t.scalar_type() == torch::kFloat32);
+    TORCH_CHECK(q.dim() == 3 && k.dim() == 3 && k.device() == q.device(),
+                "rope: q and k must be [T, heads, head_dim] on one device");
+    TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == torch::kInt32 &&
+                    pos.dim() == 1 && pos.is_contiguous(),
+                "rope: positions must be int32 [T] contiguous on GPU");
+    TORCH_CHECK(cos_t.is_cuda() && sin_t.is_cuda() &&
+                    cos_t.scalar_type() == torch::kFloat32 &&
+                    sin_t.scalar_type() == torch::kFloat32,
+                "rope: cos/sin tables must be fp32 on GPU");
     const int T = q.size(0);
     const int nq = q.size(1), nkv = k.size(1), hd = q.size(2);
-    TORCH_CHECK(k.size(2) == hd && k.size(0) == T);
+    TORCH_CHECK(hd >= 2 && hd % 2 == 0,
+                "rope: head_dim must be even and >= 2, got ", hd);
+    TORCH_CHECK(k.size(2) == hd && k.size(0) == T,
+                "rope: k must have q's token count and head_dim");
+    TORCH_CHECK(pos.size(0) == T, "rope: need one position per token, got ",
+                pos.size(0), " for ", T, " tokens");
     // heads/dims contiguous within a token; token stride may be larger
     TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == hd);
     TORCH_CHECK(k.stride(2) == 1 && k.stride(1) == hd);
-    TORCH_CHECK(cos_t.size(1) == hd / 2 && cos_t.is_contiguous() &&
-                sin_t.is_contiguous());
+    TORCH_CHECK(cos_t.dim() == 2 && cos_t.size(1) == hd / 2 &&
+                    cos_t.sizes() == sin_t.sizes() && cos_t.is_contiguous() &&
+                    sin_t.is_contiguous(),
+                "rope: cos and sin must both be [max_len, head_dim / 2] "
+                "contiguous");
+    TORCH_CHECK((long)T * (nq + nkv) <= INT_MAX);
     if (T == 0 || nq + nkv == 0) return;
     launch_rope(bf16p_mut(q), bf16p_mut(k), pos.data_ptr<int>(),
                 cos_t.data_ptr<float>(), sin_t.data_ptr<float>(), T, nq, nkv,
@@ -244,17 +260,39 @@ void kv_cache_store(const Tensor& k, const Tensor& v, Tensor& k_cache,
                     const OptTensor& k_inv_scale,
                     const OptTensor& v_inv_scale) {
     check_bf16(k, "k");
+    check_bf16(v, "v");
+    TORCH_CHECK(k.dim() == 3 && v.sizes() == k.sizes() &&
+                    v.device() == k.device(),
+                "kv_cache_store: k and v must both be [T, n_kv_heads, "
+                "head_dim] on one device");
+    TORCH_CHECK(k_cache.dim() == 4 && v_cache.sizes() == k_cache.sizes() &&
+                    v_cache.scalar_type() == k_cache.scalar_type() &&
+                    k_cache.device() == k.device() &&
+                    v_cache.device() == k.device(),
+                "kv_cache_store: the caches must be [n_blocks, n_kv_heads, "
+                "block_size, head_dim], alike in size and dtype, on k's "
+                "device");
     const bool scaled =
         check_kv_scales(k_inv_scale, v_inv_scale, k_cache, "kv_cache_store");
-    TORCH_CHECK(slots.scalar_type() == torch::kInt32);
     const int T = k.size(0), nkv = k.size(1), hd = k.size(2);
+    TORCH_CHECK(slots.is_cuda() && slots.device() == k.device() &&
+                    slots.scalar_type() == torch::kInt32 &&
+                    slots.dim() == 1 && slots.is_contiguous() &&
+                    slots.size(0) == T,
+                "kv_cache_store: slots must be int32 [T] contiguous on k's "
+                "device, T = ", T);
     const int bs = k_cache.size(2);
-    TORCH_CHECK(k_cache.size(1) == nkv && k_cache.size(3) == hd);
+    TORCH_CHECK(k_cache.size(1) == nkv && k_cache.size(3) == hd,
+                "kv_cache_store: the caches' n_kv_heads and head_dim must "
+                "be k's");
     TORCH_CHECK(k_cache.is_contiguous() && v_cache.is_contiguous());
+    TORCH_CHECK((long)T * nkv <= INT_MAX);
     TORCH_CHECK(k.stride(2) == 1 && k.stride(1) == hd);
     TORCH_CHECK(v.stride(2) == 1 && v.stride(1) == hd);
     TORCH_CHECK(hd % 2 == 0);
     if (T == 0 || nkv == 0) return;
+    TORCH_CHECK(k_cache.numel() > 0,
+                "kv_cache_store: tokens to store but an empty cache");
     if (k_cache.scalar_type() == torch::kUInt8) {
         // fp8 (OCP e4m3) cache: quantize at store time
         launch_kv_store_fp8(bf16p(k), bf16p(v),
