@@ -116,6 +116,10 @@ def serve_hf(model, model_path, port, region, api_port, device, kv_fp8,
 @click.option("--spec-decode", is_flag=True,
               help="speculative decoding (prompt-lookup + exact greedy "
                    "verification; output-invariant)")
+@click.option("--fused-sampler", is_flag=True,
+              help="sample every eligible request (greedy, or top_k 1..1024) "
+                   "with the fused batched sampler kernel: one launch per "
+                   "step whatever the parameter mix")
 @click.option("--kv-fp8", is_flag=True, help=_KV_FP8_HELP)
 @click.option("--kv-scales", default=None, metavar="PATH|checkpoint|calibrate",
               help=_KV_SCALES_HELP)
@@ -125,11 +129,13 @@ def serve_hf(model, model_path, port, region, api_port, device, kv_fp8,
 @click.option("--sliding-window", default=None, type=int, metavar="N",
               help=_SLIDING_WINDOW_HELP)
 def serve_native(model, model_path, port, region, api_port, device,
-                 spec_decode, kv_fp8, kv_scales, kv_scales_out, max_seq_len,
-                 sliding_window):
+                 spec_decode, fused_sampler, kv_fp8, kv_scales, kv_scales_out,
+                 max_seq_len, sliding_window):
     """Serve a model on the native MI355X HIP engine (alias of serve-hf)."""
     if spec_decode:
         os.environ["BEE2BEE_SPEC_DECODE"] = "1"
+    if fused_sampler:
+        os.environ["BEE2BEE_FUSED_SAMPLER"] = "1"
     _kv_env(kv_fp8, kv_scales, kv_scales_out)
     _ctx_env(max_seq_len, sliding_window)
     _serve(

@@ -13,6 +13,7 @@ import json
 import logging
 import os
 import queue
+import random
 import threading
 import time
 from dataclasses import dataclass, field
@@ -237,6 +238,10 @@ class GenerationRequest:
     error: Optional[str] = None
     cancelled: bool = False
     output_ids: List[int] = field(default_factory=list)
+    # the seed this request's rows carry into ops.sample_rows: its own
+    # sampling.seed, or one the engine drew at submit (fused_sampler);
+    # None = the request samples on the grouped torch path
+    sample_seed: Optional[int] = None
     # optional: called from the engine thread as on_emit(token_id, done);
     # when set, tokens are NOT pushed to out_queue (async consumers use this
     # to avoid one blocking thread per request)
@@ -283,8 +288,14 @@ class InferenceEngine:
         kv_dtype: str = "native",
         kv_scales: Optional[str] = None,
         sliding_window: Optional[int] = None,
+        fused_sampler: bool = False,
     ) -> None:
-        """kv_scales (fp8 KV only): None keeps unit scales; a path loads a
+        """fused_sampler: sample every eligible request (greedy, or top_k
+        1..1024) through ops.sample_rows, one launch per step whatever the
+        parameter mix; off, only requests that carry a seed take it. The
+        environment's BEE2BEE_FUSED_SAMPLER=1 switches it on too.
+
+        kv_scales (fp8 KV only): None keeps unit scales; a path loads a
         scales file written by save_kv_scales(); "checkpoint" uses the
         self_attn.k_scale / v_scale tensors of the HF checkpoint. Run
         calibrate_kv_scales() to measure them instead.
@@ -426,6 +437,17 @@ class InferenceEngine:
         self._pen_pool: Optional[torch.Tensor] = None
         self._pen_free: List[int] = []
         self._pen_slot_cache: Optional[tuple] = None  # (slots, tensor)
+        # fused sampler (ops.sample_rows): seeded requests always take it;
+        # with fused_sampler on, every eligible request does, under a seed
+        # drawn at submit from a HOST generator (the device generator stays
+        # untouched, so the legacy path's draws do not move)
+        self.fused_sampler = bool(fused_sampler) or (
+            os.environ.get("BEE2BEE_FUSED_SAMPLER") == "1")
+        self._seed_rng = random.Random(seed)
+        self._seed_lock = threading.Lock()
+        # per-row parameter tensors of the last fused call, cached against
+        # the rows' signature; pos is advanced on the device
+        self._fused_cache: Optional[dict] = None
 
         self._busy_s = 0.0       # engine-thread time inside working steps
         self._busy_steps = 0
@@ -543,6 +565,12 @@ class InferenceEngine:
         # empty prompts become [bos] at admission (engine loop); <1
         # max_new behaves as 1 (prefill completion always emits one token)
         req.max_new_tokens = max(1, int(req.max_new_tokens))
+        sp = req.sampling
+        if sp.seed is not None:
+            req.sample_seed = sp.seed % (1 << 64)
+        elif self.fused_sampler and sp.fused_eligible():
+            with self._seed_lock:
+                req.sample_seed = self._seed_rng.getrandbits(64)
         self.start()
         self._pending.put(req)
         self._wake.set()
@@ -558,13 +586,15 @@ class InferenceEngine:
         top_p: Optional[float] = None,
         top_k: Optional[int] = None,
         repetition_penalty: Optional[float] = None,
+        seed: Optional[int] = None,
     ) -> GenerationRequest:
-        """Blocking convenience wrapper: submit + drain the stream."""
+        """Blocking convenience wrapper: submit + drain the stream. With a
+        seed the sampled tokens are a function of the request alone."""
         req = GenerationRequest(
             prompt_ids=list(prompt_ids),
             max_new_tokens=max_new_tokens,
             sampling=SamplingParams.from_request(
-                temperature, top_p, top_k, repetition_penalty),
+                temperature, top_p, top_k, repetition_penalty, seed),
             stop_token_ids=tuple(stop_token_ids),
         )
         self.submit(req)
@@ -589,6 +619,7 @@ class InferenceEngine:
         top_p: Optional[float] = None,
         top_k: Optional[int] = None,
         cancel=None,
+        seed: Optional[int] = None,
     ) -> Dict[str, Any]:
         """Text-level wrapper used by the mesh service. `stop` strings
         truncate the output at the first occurrence (reference stop-word
@@ -620,7 +651,7 @@ class InferenceEngine:
         if eos is not None:
             stop_ids = (eos,)
         sp = SamplingParams.from_request(temperature, top_p, top_k,
-                                         repetition_penalty)
+                                         repetition_penalty, seed)
         req = GenerationRequest(
             prompt_ids=ids,
             max_new_tokens=max_new_tokens,
@@ -1155,6 +1186,102 @@ class InferenceEngine:
                          logits: torch.Tensor) -> torch.Tensor:
         """Sample one token per row of logits [len(acts), V] and emit it;
         returns the sampled ids on the device."""
+        fused = self._fused_rows(acts)
+        if fused is None:
+            next_dev = self._sample_grouped(acts, logits)
+        else:
+            # ONE launch for every fused row, whatever the parameter mix;
+            # rows of the grouped path ride along as greedy and are
+            # overwritten below, so the fused rows need no gather
+            next_dev = self._sample_fused(acts, logits, fused)
+            rest = [i for i, f in enumerate(fused) if not f]
+            if rest:
+                idx = self._dev(rest, torch.int64)
+                next_dev[idx] = self._sample_grouped(
+                    [acts[i] for i in rest], logits[idx])
+        # mark the freshly sampled tokens seen (one batched device scatter)
+        if self._pen_pool is not None:
+            pen_idx = [i for i, a in enumerate(acts) if a.pen_slot is not None]
+            if len(pen_idx) == len(acts):
+                self._pen_pool[
+                    self._pen_slots_t([a.pen_slot for a in acts]), next_dev
+                ] = True
+            elif pen_idx:
+                slot_t = self._pen_slots_t([acts[i].pen_slot for i in pen_idx])
+                idx_t = torch.tensor(pen_idx, dtype=torch.int64,
+                                     device=logits.device)
+                self._pen_pool[slot_t, next_dev[idx_t]] = True
+        next_ids = next_dev.cpu()  # the one host sync per step (emission)
+        now = time.time()
+        for i, a in enumerate(acts):
+            self._emit(a, int(next_ids[i]), now)
+        self._note_throughput(len(acts), now)
+        return next_dev
+
+    def _fused_rows(self, acts: List[_Active]) -> Optional[List[bool]]:
+        """Which rows sample through ops.sample_rows; None when none does.
+        A row does when its request carries a sample seed (its own, or one
+        drawn at submit under fused_sampler), unless it needs a penalty
+        mask and the seen pool had no row left for it."""
+        if not any(a.req.sample_seed is not None for a in acts):
+            return None
+        fused = [
+            a.req.sample_seed is not None and (
+                a.req.sampling.repetition_penalty == 1.0
+                or a.pen_slot is not None)
+            for a in acts
+        ]
+        return fused if any(fused) else None
+
+    def _sample_fused(self, acts: List[_Active], logits: torch.Tensor,
+                      fused: List[bool]) -> torch.Tensor:
+        """One ops.sample_rows call over all rows of logits. The per-row
+        parameter tensors are cached against the rows' signature; while it
+        holds, only pos moves, on the device. No [rows, V] gather: the seen
+        pool and the slot indices go straight in."""
+        from .. import ops
+
+        sig = tuple((a.seq_id, f) for a, f in zip(acts, fused))
+        pos = [len(a.req.output_ids) if f else 0
+               for a, f in zip(acts, fused)]
+        c = self._fused_cache
+        if c is not None and c["sig"] == sig and c["pos"] == pos:
+            c["pos_t"].add_(c["step"])
+        else:
+            temp, topk, topp, pen, slot, seed, step = [], [], [], [], [], [], []
+            for a, f in zip(acts, fused):
+                t, k, p, rp = (a.req.sampling.fused_row() if f
+                               else (1.0, 1, 1.0, 1.0))
+                temp.append(t)
+                topk.append(k)
+                topp.append(p)
+                pen.append(rp)
+                slot.append(a.pen_slot if f and a.pen_slot is not None
+                            and rp != 1.0 else -1)
+                s = a.req.sample_seed if f else 0
+                seed.append(s - (1 << 64) if s >= (1 << 63) else s)
+                step.append(1 if f else 0)
+            fl = self._dev([temp, topp, pen], torch.float32)
+            it = self._dev([topk, slot, pos, step], torch.int32)
+            c = self._fused_cache = {
+                "sig": sig, "temp": fl[0], "topp": fl[1], "pen": fl[2],
+                "topk": it[0], "slot": it[1], "pos_t": it[2], "step": it[3],
+                "seed": self._dev(seed, torch.int64),
+                "use_pool": any(s >= 0 for s in slot),
+            }
+        # where this call leaves the host's view of pos, if every fused row
+        # emits its token
+        c["pos"] = [p + 1 if f else 0 for p, f in zip(pos, fused)]
+        return ops.sample_rows(
+            logits, c["temp"], c["topk"], c["topp"], c["pen"],
+            self._pen_pool if c["use_pool"] else None, c["slot"], c["seed"],
+            c["pos_t"])
+
+    def _sample_grouped(self, acts: List[_Active],
+                        logits: torch.Tensor) -> torch.Tensor:
+        """The grouped torch path: one sample() per distinct parameter set,
+        every row drawing from the engine-wide device generator. Returns
+        the sampled ids [len(acts)] on the device."""
         # group rows by sampling params so each group is one sample() call
         groups: Dict[tuple, List[int]] = {}
         for i, a in enumerate(acts):
@@ -1215,23 +1342,6 @@ class InferenceEngine:
                 next_dev = toks
             else:
                 next_dev[idx] = toks
-        # mark the freshly sampled tokens seen (one batched device scatter)
-        if self._pen_pool is not None:
-            pen_idx = [i for i, a in enumerate(acts) if a.pen_slot is not None]
-            if len(pen_idx) == len(acts):
-                self._pen_pool[
-                    self._pen_slots_t([a.pen_slot for a in acts]), next_dev
-                ] = True
-            elif pen_idx:
-                slot_t = self._pen_slots_t([acts[i].pen_slot for i in pen_idx])
-                idx_t = torch.tensor(pen_idx, dtype=torch.int64,
-                                     device=logits.device)
-                self._pen_pool[slot_t, next_dev[idx_t]] = True
-        next_ids = next_dev.cpu()  # the one host sync per step (emission)
-        now = time.time()
-        for i, a in enumerate(acts):
-            self._emit(a, int(next_ids[i]), now)
-        self._note_throughput(len(acts), now)
         return next_dev
 
     def stats(self) -> Dict[str, Any]:

@@ -1,5 +1,9 @@
 """Token sampling: greedy, temperature, top-k/top-p — device-side torch ops
-on [B, V] logits (the per-step cost is dwarfed by the lm_head GEMM).
+on [B, V] logits (the per-step cost is dwarfed by the lm_head GEMM). This
+is the grouped path: unseeded requests, engine-wide generator. Requests that
+carry a seed, and every eligible request under the engine's fused_sampler
+option, sample through ops.sample_rows instead (one launch per step,
+per-row parameters, RNG keyed by (seed, output position)).
 
 Matches the reference generation knobs (bee2bee/hf.py:94-103: temperature,
 top_p 0.95, repetition_penalty 1.15)."""
@@ -10,6 +14,25 @@ from typing import Optional
 
 import torch
 
+# the fused sampler (ops.sample_rows) keeps at most this many candidates
+from ..ops.reference import SAMPLE_MAX_K as FUSED_MAX_TOP_K
+
+
+def sanitize_seed(seed) -> Optional[int]:
+    """A request's `seed` -> an int in [0, 2^64), or None (unseeded).
+    Integers (and floats with an integral value) are taken mod 2^64;
+    anything else, bools and NaN/inf included, is None."""
+    if isinstance(seed, bool):
+        return None
+    if isinstance(seed, float):
+        if seed != seed or seed in (float("inf"), float("-inf")) \
+                or seed != int(seed):
+            return None
+        seed = int(seed)
+    if not isinstance(seed, int):
+        return None
+    return seed % (1 << 64)
+
 
 @dataclass
 class SamplingParams:
@@ -18,6 +41,23 @@ class SamplingParams:
     top_k: int = 64
     repetition_penalty: float = 1.0
     greedy: bool = False
+    # a seeded request samples through ops.sample_rows with a counter-based
+    # RNG keyed by (seed, output position): the same tokens in any batch
+    seed: Optional[int] = None
+
+    def fused_eligible(self) -> bool:
+        """Whether ops.sample_rows expresses these params exactly."""
+        return self.greedy or 1 <= self.top_k <= FUSED_MAX_TOP_K
+
+    def fused_row(self):
+        """(temperature, top_k, top_p, penalty) as ops.sample_rows takes
+        them: greedy is top_k 1 at temperature 1, and a top_k the kernel
+        cannot hold (0 = off, or above 1024) is served with 1024."""
+        if self.greedy:
+            return 1.0, 1, 1.0, self.repetition_penalty
+        k = self.top_k if 1 <= self.top_k <= FUSED_MAX_TOP_K \
+            else FUSED_MAX_TOP_K
+        return self.temperature, k, self.top_p, self.repetition_penalty
 
     @classmethod
     def from_request(
@@ -26,6 +66,7 @@ class SamplingParams:
         top_p: Optional[float] = None,
         top_k: Optional[int] = None,
         repetition_penalty: Optional[float] = None,
+        seed=None,
     ) -> "SamplingParams":
         """Wire/API request knobs -> params, with the REFERENCE's generation
         defaults (bee2bee/hf.py:94-103): temperature 0.7, top_p 0.95,
@@ -44,6 +85,7 @@ class SamplingParams:
         rp = (1.15 if repetition_penalty is None
               else float(repetition_penalty))
         p.repetition_penalty = rp if math.isfinite(rp) and rp > 0 else 1.15
+        p.seed = sanitize_seed(seed)
         return p
 
 

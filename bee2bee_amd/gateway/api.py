@@ -10,7 +10,7 @@ from __future__ import annotations
 import asyncio
 import os
 import time
-from typing import List, Optional
+from typing import Any, List, Optional
 
 from fastapi import Depends, FastAPI, HTTPException, status
 from fastapi.middleware.cors import CORSMiddleware
@@ -129,6 +129,9 @@ class ChatRequest(BaseModel):
     top_p: Optional[float] = None
     top_k: Optional[int] = None
     repetition_penalty: Optional[float] = None
+    # an integer makes the sampled completion reproducible; anything else
+    # reads as absent (unseeded), never as an error
+    seed: Optional[Any] = None
     stream: Optional[bool] = False
 
 
@@ -234,6 +237,7 @@ async def chat(req: ChatRequest):
                 "top_p": req.top_p,
                 "top_k": req.top_k,
                 "repetition_penalty": req.repetition_penalty,
+                "seed": req.seed,
             }
             if req.stream:
                 if hasattr(svc, "execute_stream_async"):
@@ -288,7 +292,8 @@ async def chat(req: ChatRequest):
             pid, req.prompt, req.max_new_tokens or 2048, req.model,
             temperature=req.temperature or 0.7,
             sampling={"top_p": req.top_p, "top_k": req.top_k,
-                      "repetition_penalty": req.repetition_penalty},
+                      "repetition_penalty": req.repetition_penalty,
+                      "seed": req.seed},
         )
         return {
             "status": "ok",

@@ -39,6 +39,8 @@ class CompletionRequest(BaseModel):
     max_tokens: Optional[int] = 256
     temperature: Optional[float] = None
     top_p: Optional[float] = None
+    # OpenAI's `seed`: the same seed and parameters give the same completion
+    seed: Optional[Any] = None
     stream: Optional[bool] = False
     n: Optional[int] = 1
     stop: Optional[Any] = None  # str | List[str]
@@ -55,6 +57,8 @@ class ChatCompletionRequest(BaseModel):
     max_tokens: Optional[int] = 256
     temperature: Optional[float] = None
     top_p: Optional[float] = None
+    # OpenAI's `seed`: the same seed and parameters give the same completion
+    seed: Optional[Any] = None
     stream: Optional[bool] = False
     n: Optional[int] = 1
     stop: Optional[Any] = None
@@ -108,6 +112,9 @@ async def _run_buffered(node, model: Optional[str], prompt: str,
     }
     if req.top_p is not None:
         params["top_p"] = req.top_p
+    seed = getattr(req, "seed", None)
+    if seed is not None:
+        params["seed"] = seed
     svc = _pick_service(node, model)
     loop = asyncio.get_running_loop()
     if svc is not None:
@@ -117,7 +124,7 @@ async def _run_buffered(node, model: Optional[str], prompt: str,
     return await node.request_generation(
         pid, prompt, params["max_new_tokens"], model,
         temperature=params["temperature"],
-        sampling={"top_p": req.top_p},
+        sampling={"top_p": req.top_p, "seed": seed},
     )
 
 
@@ -140,6 +147,8 @@ async def _stream_deltas(node, model, prompt, req) -> AsyncIterator[str]:
         }
         if req.top_p is not None:
             params["top_p"] = req.top_p
+        if getattr(req, "seed", None) is not None:
+            params["seed"] = req.seed
         loop = asyncio.get_running_loop()
         queue: asyncio.Queue = asyncio.Queue()
 

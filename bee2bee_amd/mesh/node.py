@@ -567,8 +567,8 @@ class MeshNode:
                         max_new_tokens=params["max_new_tokens"],
                         model_name=model_name,
                         temperature=params.get("temperature", 0.7),
-                        sampling={k: params.get(k) for k in
-                                  ("top_p", "top_k", "repetition_penalty")},
+                        sampling={k: params.get(k)
+                                  for k in wire.SAMPLING_KEYS},
                         stream=want_stream,
                         on_chunk=_forward_chunk if want_stream else None,
                         hops=hops + 1,
@@ -849,7 +849,7 @@ class MeshNode:
                     "max_new_tokens": max_new_tokens,
                     "temperature": temperature,
                 }
-                for key in ("top_p", "top_k", "repetition_penalty"):
+                for key in wire.SAMPLING_KEYS:
                     if sampling and sampling.get(key) is not None:
                         params[key] = sampling[key]
                 loop = asyncio.get_running_loop()

@@ -97,6 +97,12 @@ def service_announce(name: str, meta: Dict[str, Any]) -> Dict[str, Any]:
     return {"type": SERVICE_ANNOUNCE, "service": name, "meta": meta}
 
 
+# optional sampling knobs of a gen_request; an absent key means the
+# engine's default (for seed: unseeded), and old peers ignore keys they do
+# not know
+SAMPLING_KEYS = ("top_p", "top_k", "repetition_penalty", "seed")
+
+
 def gen_request(
     rid: str,
     prompt: str,
@@ -122,7 +128,7 @@ def gen_request(
     }
     # optional sampling knobs ride alongside (request_params reads the same
     # keys on the receiving side; absent -> reference generation defaults)
-    for key in ("top_p", "top_k", "repetition_penalty"):
+    for key in SAMPLING_KEYS:
         if sampling and sampling.get(key) is not None:
             frame[key] = sampling[key]
     if hops:
@@ -167,7 +173,7 @@ def request_params(data: Dict[str, Any]) -> Dict[str, Any]:
     }
     # optional sampling knobs pass through when present (None -> the
     # engine applies the reference generation defaults)
-    for key in ("top_p", "top_k", "repetition_penalty"):
+    for key in SAMPLING_KEYS:
         if data.get(key) is not None:
             out[key] = data[key]
     return out

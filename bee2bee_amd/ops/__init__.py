@@ -10,7 +10,7 @@ GPU-less plumbing runs).
 Kernels (ops/csrc/): fused (add+)RMSNorm, RoPE, fused per-head QK-norm +
 RoPE (Qwen3), paged KV store, paged GQA
 decode attention (flash-decoding style), MFMA flash prefill attention,
-SwiGLU, top-k gating, grouped expert GEMM. Plain projection GEMMs go
+SwiGLU, top-k gating, grouped expert GEMM, seeded batched sampling. Plain projection GEMMs go
 through hipBLASLt via torch.nn.functional.linear — library GEMMs are the
 one place we use a vendor library; every fused hot op is hand-written HIP.
 
@@ -333,3 +333,33 @@ def grouped_gemm(
     if _use_hip(x):
         return require_hip().grouped_gemm(x, w, offsets)
     return reference.grouped_gemm(x, w, offsets)
+
+
+def sample_rows(
+    logits: torch.Tensor,
+    temperature: torch.Tensor,
+    top_k: torch.Tensor,
+    top_p: torch.Tensor,
+    penalty: torch.Tensor,
+    seen_pool: Optional[torch.Tensor],
+    seen_slot: torch.Tensor,
+    seed: torch.Tensor,
+    pos: torch.Tensor,
+) -> torch.Tensor:
+    """Seeded per-row sampling, logits [B, V] bf16 | fp32 -> int64 [B]; the
+    semantics are reference.sample_rows. Per row: temperature f32, top_k
+    i32 (clamped to 1..min(V, 1024); greedy is top_k 1, temperature 1),
+    top_p f32, penalty f32, seen_slot i32 (row of seen_pool bool/uint8
+    [S, V], -1 = none), seed i64 and pos i32: the draw is a function of
+    (seed, pos) alone, so a row samples the same token in any batch.
+
+    One HIP launch, one workgroup per row, any row stride; graph-safe (all
+    parameters are device tensors). The binding checks shapes, dtypes and
+    devices. It cannot check VALUES without a sync: top_k and seen_slot
+    out of range are clamped in the kernel (a slot >= S reads as -1)."""
+    if _use_hip(logits):
+        return require_hip().sample_rows(
+            logits, temperature, top_k, top_p, penalty, seen_pool, seen_slot,
+            seed, pos)
+    return reference.sample_rows(logits, temperature, top_k, top_p, penalty,
+                                 seen_pool, seen_slot, seed, pos)

@@ -66,6 +66,11 @@ void launch_bw_rowperinstr(const unsigned short*, long, int, int, float*,
                            hipStream_t);
 void launch_bw_paged(const unsigned short*, const int*, long, int, int,
                      float*, hipStream_t);
+void launch_sample_rows(const void*, int, long, int, int, const float*,
+                        const int*, const float*, const float*,
+                        const unsigned char*, long, int, const int*,
+                        const long long*, const int*, long long*,
+                        hipStream_t);
 }
 
 namespace {
@@ -588,6 +593,79 @@ Tensor grouped_gemm(const Tensor& x, const Tensor& w, const Tensor& offs) {
     return out;
 }
 
+// Seeded per-row sampling (sample.hip): logits [B, V] bf16 | fp32 with any
+// row stride -> int64 [B]. Every per-row parameter is a device tensor, so
+// nothing here reads a value; top_k and seen_slot values out of range are
+// clamped by the kernel.
+Tensor sample_rows(const Tensor& logits, const Tensor& temperature,
+                   const Tensor& top_k, const Tensor& top_p,
+                   const Tensor& penalty, const OptTensor& seen_pool,
+                   const Tensor& seen_slot, const Tensor& seed,
+                   const Tensor& pos) {
+    TORCH_CHECK(logits.is_cuda(), "sample_rows: logits must be on GPU");
+    const bool f32 = logits.scalar_type() == torch::kFloat32;
+    TORCH_CHECK(f32 || logits.scalar_type() == torch::kBFloat16,
+                "sample_rows: logits must be bf16 or fp32");
+    TORCH_CHECK(logits.dim() == 2, "sample_rows: logits must be [B, V]");
+    const long B = logits.size(0), V = logits.size(1);
+    TORCH_CHECK(V >= 1 && V <= INT_MAX && B <= INT_MAX,
+                "sample_rows: need 1 <= V and B, V within int32");
+    TORCH_CHECK(logits.stride(1) == 1 || V == 1,
+                "sample_rows: the last dimension of logits must be "
+                "contiguous (any row stride is fine)");
+    TORCH_CHECK(B <= 1 || logits.stride(0) >= 0,
+                "sample_rows: negative row stride");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) %
+                        logits.element_size() == 0,
+                "sample_rows: logits are not element-aligned");
+    struct Row { const Tensor* t; torch::ScalarType ty; const char* name; };
+    const Row rows[] = {{&temperature, torch::kFloat32, "temperature (fp32)"},
+                        {&top_k, torch::kInt32, "top_k (int32)"},
+                        {&top_p, torch::kFloat32, "top_p (fp32)"},
+                        {&penalty, torch::kFloat32, "penalty (fp32)"},
+                        {&seen_slot, torch::kInt32, "seen_slot (int32)"},
+                        {&seed, torch::kInt64, "seed (int64)"},
+                        {&pos, torch::kInt32, "pos (int32)"}};
+    for (const Row& r : rows)
+        TORCH_CHECK(r.t->is_cuda() && r.t->device() == logits.device() &&
+                        r.t->scalar_type() == r.ty && r.t->dim() == 1 &&
+                        r.t->size(0) == B && r.t->is_contiguous(),
+                    "sample_rows: ", r.name, " must be [B] contiguous on the "
+                    "logits' device, B = ", B);
+    const unsigned char* pool = nullptr;
+    long pool_stride = 0;
+    int n_slots = 0;
+    if (seen_pool.has_value()) {
+        const Tensor& sp = *seen_pool;
+        TORCH_CHECK(sp.is_cuda() && sp.device() == logits.device() &&
+                        (sp.scalar_type() == torch::kBool ||
+                         sp.scalar_type() == torch::kUInt8),
+                    "sample_rows: seen_pool must be bool or uint8 on the "
+                    "logits' device");
+        TORCH_CHECK(sp.dim() == 2 && sp.size(1) == V && sp.size(0) >= 1 &&
+                        sp.size(0) <= INT_MAX && sp.is_contiguous(),
+                    "sample_rows: seen_pool must be [S, V] contiguous, "
+                    "S >= 1, V = ", V);
+        pool = static_cast<const unsigned char*>(sp.data_ptr());
+        pool_stride = V;
+        n_slots = (int)sp.size(0);
+    }
+    Tensor out = torch::empty({B}, logits.options().dtype(torch::kInt64));
+    if (B == 0) return out;
+    launch_sample_rows(logits.data_ptr(), f32 ? 1 : 0, logits.stride(0),
+                       (int)B, (int)V, temperature.data_ptr<float>(),
+                       top_k.data_ptr<int>(), top_p.data_ptr<float>(),
+                       penalty.data_ptr<float>(), pool, pool_stride, n_slots,
+                       seen_slot.data_ptr<int>(),
+                       reinterpret_cast<const long long*>(
+                           seed.data_ptr<int64_t>()),
+                       pos.data_ptr<int>(),
+                       reinterpret_cast<long long*>(out.data_ptr<int64_t>()),
+                       stream());
+    check_launch("sample_rows");
+    return out;
+}
+
 Tensor mfma_probe_fp8(const Tensor& A, const Tensor& B) {
     TORCH_CHECK(A.scalar_type() == torch::kUInt8 &&
                 B.scalar_type() == torch::kUInt8);
@@ -686,6 +764,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("seq_lens"), py::arg("cu_q"), py::arg("max_qlen"),
           py::arg("scale"), py::arg("k_scale") = py::none(),
           py::arg("v_scale") = py::none(), py::arg("window") = 0);
+    m.def("sample_rows", &sample_rows,
+          "seeded per-row temperature / top-k / top-p / penalty sampling",
+          py::arg("logits"), py::arg("temperature"), py::arg("top_k"),
+          py::arg("top_p"), py::arg("penalty"), py::arg("seen_pool"),
+          py::arg("seen_slot"), py::arg("seed"), py::arg("pos"));
     m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
     m.def("mfma_probe_fp8", &mfma_probe_fp8,
           "16x16x32 fp8 MFMA layout probe");

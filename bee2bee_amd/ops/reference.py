@@ -423,3 +423,134 @@ def attn_decode_lse(
                       out_ml=out_ml, k_scale=k_scale, v_scale=v_scale,
                       window=window)
     return out, out_ml
+
+
+# ------------------------------------------------------------------ sampling
+
+SAMPLE_MAX_K = 1024  # candidates the sampler keeps at most (kernel LDS sort)
+
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_U32 = 0xFFFFFFFF
+
+
+def _mulhilo32(a: int, b: torch.Tensor):
+    """(hi, lo) words of the 64-bit product a * b; b holds u32 values in
+    int64, and no intermediate leaves int64."""
+    lo16 = a * (b & 0xFFFF)
+    t = a * (b >> 16) + (lo16 >> 16)
+    return t >> 16, ((t & 0xFFFF) << 16) | (lo16 & 0xFFFF)
+
+
+def philox4x32(counter, key, rounds: int = 10) -> torch.Tensor:
+    """Philox4x32 (Salmon et al., SC'11). counter [..., 4] and key [..., 2]
+    hold u32 words as int64; returns the four output words [..., 4]."""
+    c = [torch.as_tensor(counter, dtype=torch.int64)[..., i] & _U32
+         for i in range(4)]
+    k = [torch.as_tensor(key, dtype=torch.int64)[..., i] & _U32
+         for i in range(2)]
+    for r in range(rounds):
+        if r:
+            k = [(k[0] + _PHILOX_W0) & _U32, (k[1] + _PHILOX_W1) & _U32]
+        hi0, lo0 = _mulhilo32(_PHILOX_M0, c[0])
+        hi1, lo1 = _mulhilo32(_PHILOX_M1, c[2])
+        c = [hi1 ^ c[1] ^ k[0], lo1, hi0 ^ c[3] ^ k[1], lo0]
+    return torch.stack(c, dim=-1)
+
+
+def sample_uniform(seed: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
+    """The sampler's draw u in (0, 1] for (seed int64, pos int32), fp32:
+    word 0 of Philox4x32-10 under key (seed_lo, seed_hi) and counter
+    (pos, 0, 0, 0), as ((r0 >> 8) + 0.5) * 2^-24 in fp32 arithmetic."""
+    seed = seed.to(torch.int64)
+    key = torch.stack([seed & _U32, (seed >> 32) & _U32], dim=-1)
+    p = pos.to(torch.int64) & _U32
+    zero = torch.zeros_like(p)
+    r0 = philox4x32(torch.stack([p, zero, zero, zero], dim=-1), key)[..., 0]
+    return ((r0 >> 8).to(torch.float32) + 0.5) * (2.0 ** -24)
+
+
+def sample_sort_key(z: torch.Tensor) -> torch.Tensor:
+    """Order-preserving u32 key of fp32 z (as int64): larger z, larger key;
+    -0.0 counts as +0.0 and every NaN maps to key 0, below -inf."""
+    z = z + 0.0
+    bits = z.contiguous().view(torch.int32).to(torch.int64) & _U32
+    key = torch.where(bits >= 0x80000000, ~bits & _U32, bits | 0x80000000)
+    return torch.where(torch.isnan(z), torch.zeros_like(key), key)
+
+
+def sample_z(logits, temperature, penalty, seen_pool, seen_slot):
+    """Steps 1 and 2 of sample_rows: the penalized, temperature-scaled
+    logits z, fp32 [B, V]."""
+    x = logits.float()
+    if seen_pool is not None:
+        slot = seen_slot.to(torch.int64)
+        seen = seen_pool[slot.clamp_min(0)].bool() & (slot >= 0)[:, None]
+        p = penalty.float()[:, None]
+        x = torch.where(seen, torch.where(x > 0, x / p, x * p), x)
+    t = temperature.float()
+    t = torch.where(t > 1e-5, t, torch.full_like(t, 1e-5))
+    return x / t[:, None] + 0.0
+
+
+def sample_rows(
+    logits: torch.Tensor,
+    temperature: torch.Tensor,
+    top_k: torch.Tensor,
+    top_p: torch.Tensor,
+    penalty: torch.Tensor,
+    seen_pool: Optional[torch.Tensor],
+    seen_slot: torch.Tensor,
+    seed: torch.Tensor,
+    pos: torch.Tensor,
+) -> torch.Tensor:
+    """Seeded per-row sampling: logits [B, V] bf16 | fp32 -> int64 [B].
+
+    Every row has its own temperature f32, top_k i32, top_p f32, penalty
+    f32, seen_slot i32 (row of seen_pool bool/uint8 [S, V]; -1 = none),
+    seed i64 and pos i32. Per row:
+
+      1. x = float(logit); a token whose seen bit is set becomes x / penalty
+         if x > 0, else x * penalty.
+      2. z = x / max(T, 1e-5), in fp32.
+      3. The candidates are the k = clamp(top_k, 1, min(V, 1024)) largest
+         under the total order (z descending, index ascending).
+      4. w_j = exp(z_j - z_0) over the candidates in that order.
+      5. With 0 < top_p < 1, candidate j stays while
+         (cum_j - w_j) / Z <= top_p (the token that crosses top_p stays).
+      6. u = sample_uniform(seed, pos); the result is the first kept j with
+         cum_j > u * Z_kept, or the last kept one.
+
+    Greedy is top_k = 1, temperature = 1: the argmax, lowest index on a tie.
+    Non-finite values: -0.0 orders as +0.0 and NaN orders below -inf
+    (sample_sort_key); a NaN candidate has weight 0; and when the first
+    candidate is not finite (+inf, or a row without a finite entry) it is
+    the result, so such a row gives its lowest-index +inf, else token 0.
+    A NaN temperature reads as 1e-5 and a NaN top_p as off."""
+    B, V = logits.shape
+    dev = logits.device
+    z = sample_z(logits, temperature, penalty, seen_pool, seen_slot)
+    kmax = min(V, SAMPLE_MAX_K)
+    k = top_k.to(torch.int64).clamp(1, kmax)
+    order = torch.sort(sample_sort_key(z), dim=1, descending=True,
+                       stable=True).indices[:, :kmax]
+    zc = z.gather(1, order)
+    j = torch.arange(kmax, device=dev)[None, :]
+    valid = j < k[:, None]
+    z0 = zc[:, :1]
+    w = torch.where(valid & ~torch.isnan(zc), torch.exp(zc - z0),
+                    torch.zeros_like(zc))
+    w = torch.where(torch.isnan(w), torch.zeros_like(w), w)
+    cum = torch.cumsum(w, dim=1, dtype=torch.float32)
+    Z = cum.gather(1, (k - 1)[:, None])
+    p = top_p.float()[:, None]
+    keep = valid & (~((p > 0) & (p < 1)) | ((cum - w) / Z <= p))
+    n_kept = keep.to(torch.int64).cumprod(dim=1).sum(dim=1).clamp_min(1)
+    thr = sample_uniform(seed, pos).to(dev)[:, None] * cum.gather(
+        1, (n_kept - 1)[:, None])
+    hit = (cum > thr) & (j < n_kept[:, None])
+    first = torch.where(hit, j, torch.full_like(j, kmax)).amin(dim=1)
+    choice = torch.minimum(first, n_kept - 1)
+    choice = torch.where(torch.isfinite(z0[:, 0]), choice,
+                         torch.zeros_like(choice))
+    return order.gather(1, choice[:, None])[:, 0]

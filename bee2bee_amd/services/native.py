@@ -75,6 +75,10 @@ class NativeEngineService(BaseService):
                 # small quantization cost; serving opt-in
                 kv_dtype="fp8" if kv_fp8 else "native",
                 kv_scales=None if calibrate else kv_scales,
+                # fused batched sampler for every eligible request; off,
+                # only requests that carry a seed take it
+                fused_sampler=(
+                    os.environ.get("BEE2BEE_FUSED_SAMPLER") == "1"),
             )
             if calibrate:
                 from ..engine.engine import default_calibration_prompts
@@ -128,6 +132,12 @@ class NativeEngineService(BaseService):
             "top_p": None if tp is None else float(tp),
             "top_k": None if tk is None else int(tk),
         }
+        # an absent (or unusable) seed leaves the request unseeded
+        from ..engine.sampler import sanitize_seed
+
+        seed = sanitize_seed(params.get("seed"))
+        if seed is not None:
+            extra["seed"] = seed
         return prompt, max_new, temperature, extra
 
     def execute(self, params: Dict[str, Any]) -> Dict[str, Any]:
@@ -204,7 +214,7 @@ class NativeEngineService(BaseService):
         ids = ids[-(eng.max_seq_len - max_new - 1):]
         sp = SamplingParams.from_request(
             temperature, extra.get("top_p"), extra.get("top_k"),
-            extra.get("repetition_penalty"))
+            extra.get("repetition_penalty"), extra.get("seed"))
         stop_ids = ()
         eos = getattr(eng.tokenizer, "eos_token_id", None)
         if eos is not None:

@@ -24,6 +24,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "attn_prefill.hip"),
         os.path.join(CSRC, "probe.hip"),
         os.path.join(CSRC, "grouped_gemm.hip"),
+        os.path.join(CSRC, "sample.hip"),
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"]
