@@ -122,21 +122,29 @@ class Runner:
         q = q.view(T, s.n_heads, s.head_dim)
         k = k.view(T, s.n_kv_heads, s.head_dim)
         v = v.view(T, s.n_kv_heads, s.head_dim)
-        if s.qk_norm:  # Qwen3: per-head RMSNorm of q and k, fused with RoPE
-            ops.qk_norm_rope_inplace(q, k, positions, self.rope_cos,
-                                     self.rope_sin, lw.q_norm, lw.k_norm,
-                                     s.rms_eps)
-        elif s.pos_type == "rope":
-            ops.rope_inplace(q, k, positions, self.rope_cos, self.rope_sin)
-        if self.kv_observer is not None:
-            self.kv_observer(layer_idx, k, v)
         k_cache, v_cache = self.kv.layer(layer_idx)
         sc = self.kv.layer_scales(layer_idx)
-        if sc is None:
-            ops.kv_cache_store(k, v, k_cache, v_cache, slot_mapping)
-        else:  # fp8 cache: per-kv-head scales (all ones until calibrated)
+        # fp8 cache: per-kv-head scales (all ones until calibrated)
+        scale_kw = {} if sc is None else dict(k_inv_scale=sc[2],
+                                              v_inv_scale=sc[3])
+        if (s.pos_type == "rope" and not s.qk_norm
+                and self.kv_observer is None):
+            # RoPE and the cache append in one pass over q, k, v
+            ops.rope_kv_store(q, k, v, positions, self.rope_cos,
+                              self.rope_sin, k_cache, v_cache, slot_mapping,
+                              **scale_kw)
+        else:  # the calibration hook sits between the two calls
+            if s.qk_norm:  # Qwen3: per-head RMSNorm of q and k, with RoPE
+                ops.qk_norm_rope_inplace(q, k, positions, self.rope_cos,
+                                         self.rope_sin, lw.q_norm, lw.k_norm,
+                                         s.rms_eps)
+            elif s.pos_type == "rope":
+                ops.rope_inplace(q, k, positions, self.rope_cos,
+                                 self.rope_sin)
+            if self.kv_observer is not None:
+                self.kv_observer(layer_idx, k, v)
             ops.kv_cache_store(k, v, k_cache, v_cache, slot_mapping,
-                               k_inv_scale=sc[2], v_inv_scale=sc[3])
+                               **scale_kw)
         attn_out = attn_fn(layer_idx, q, k, v, k_cache, v_cache)
         attn_out = F.linear(attn_out.reshape(T, s.q_size), lw.wo, lw.wo_bias)
         if self.tp_group is not None:

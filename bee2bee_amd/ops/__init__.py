@@ -166,6 +166,37 @@ def kv_cache_store(
                              k_inv_scale, v_inv_scale)
 
 
+def rope_kv_store(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    positions: torch.Tensor,
+    cos: torch.Tensor,
+    sin: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    slot_mapping: torch.Tensor,
+    k_inv_scale: Optional[torch.Tensor] = None,
+    v_inv_scale: Optional[torch.Tensor] = None,
+) -> None:
+    """Exactly rope_inplace(q, k, positions, cos, sin) followed by
+    kv_cache_store(k, v, k_cache, v_cache, slot_mapping, k_inv_scale,
+    v_inv_scale), bit for bit: q and k end rotated in place, and the cache
+    holds the rotated k and v. On the GPU it is one kernel that reads q, k
+    and v once (head_dim % 16 == 0, token strides that are multiples of 8,
+    16-byte-aligned bases) and the two kernels of the separate ops for any
+    other layout. The binding makes every check of both ops before any
+    launch; the contracts on the VALUES of `positions` and `slot_mapping`
+    are those of the two ops."""
+    if _use_hip(q):
+        require_hip().rope_kv_store(q, k, v, positions, cos, sin, k_cache,
+                                    v_cache, slot_mapping, k_inv_scale,
+                                    v_inv_scale)
+        return
+    reference.rope_kv_store(q, k, v, positions, cos, sin, k_cache, v_cache,
+                            slot_mapping, k_inv_scale, v_inv_scale)
+
+
 def attn_decode(
     q: torch.Tensor,
     k_cache: torch.Tensor,

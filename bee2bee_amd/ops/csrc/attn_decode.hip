@@ -82,18 +82,44 @@ static_assert(DEC_CHUNK == DEC_WAVES * WAVE && DEC_CHUNK == DEC_BLOCK,
 // wave less (docs/KERNELS.md, "Shared stages").
 #define DEC_LDS __attribute__((address_space(3)))
 
+// Cache policy of the KV stream. A decode step reads every K and V byte
+// once, so nothing is gained by keeping them in L2 or the Infinity Cache.
+// With a switch at 1 the decode kernels read that stream with non-temporal
+// loads (the `nt` bit on global_load). Every K read goes through load_kfrag
+// or load_kv_bf16x8 and every V read through load_v_pair, so a switch
+// changes the load flavour and nothing else: registers, occupancy and every
+// output bit stay what they are at 0. The shipped values follow the
+// measurements in docs/KERNELS.md, "Cache policy of the KV stream".
+#ifndef DEC_K_NT
+#define DEC_K_NT 0
+#endif
+#ifndef DEC_V_NT
+#define DEC_V_NT 1
+#endif
+template <bool NT, typename T>
+__device__ __forceinline__ T dec_ld(const T* p) {
+    if constexpr (NT) return __builtin_nontemporal_load(p);
+    else return *p;
+}
+
 // KV element loaders, templated on the cache storage type:
 //   unsigned short = bf16 (2 B/elem), unsigned char = OCP fp8 e4m3 (1 B).
+// load_kv_bf16x8: 8 K elements for the generic scores kernel.
 template <typename KVT>
 __device__ __forceinline__ bf16x8 load_kv_bf16x8(const KVT* p);
 template <>
 __device__ __forceinline__ bf16x8 load_kv_bf16x8(const unsigned short* p) {
-    return *reinterpret_cast<const bf16x8*>(p);
+    return dec_ld<DEC_K_NT>(reinterpret_cast<const bf16x8*>(p));
 }
 template <>
 __device__ __forceinline__ bf16x8 load_kv_bf16x8(const unsigned char* p) {
     float f[8];
+#if DEC_K_NT
+    const uchar8 raw = dec_ld<true>(reinterpret_cast<const uchar8*>(p));
+    load_fp8x8(reinterpret_cast<const unsigned char*>(&raw), f);
+#else
     load_fp8x8(p, f);
+#endif
     bf16x8 r;
 #pragma unroll
     for (int e = 0; e < 8; ++e) r[e] = (__bf16)f[e];
@@ -104,6 +130,13 @@ __device__ __forceinline__ bf16x8 load_kv_bf16x8(const unsigned char* p) {
 template <typename KVT> struct kv_pair_t;
 template <> struct kv_pair_t<unsigned short> { short2v v; };
 template <> struct kv_pair_t<unsigned char> { u8x2 v; };
+// one V pair: the only way the PV loops read the V cache
+template <typename KVT>
+__device__ __forceinline__ kv_pair_t<KVT> load_v_pair(const KVT* p) {
+    kv_pair_t<KVT> r;
+    r.v = dec_ld<DEC_V_NT>(reinterpret_cast<const decltype(r.v)*>(p));
+    return r;
+}
 __device__ __forceinline__ float2v kv_pair_f32(kv_pair_t<unsigned short> p) {
     return float2v{bf2f((unsigned short)p.v[0]), bf2f((unsigned short)p.v[1])};
 }
@@ -124,7 +157,8 @@ template <> struct kfrag_of<unsigned char> { using type = long; };
 template <typename KVT>
 __device__ __forceinline__ typename kfrag_of<KVT>::type load_kfrag(
     const KVT* p) {
-    return *reinterpret_cast<const typename kfrag_of<KVT>::type*>(p);
+    return dec_ld<DEC_K_NT>(
+        reinterpret_cast<const typename kfrag_of<KVT>::type*>(p));
 }
 template <typename KVT>
 __device__ __forceinline__ typename kfrag_of<KVT>::type qfrag_from_lds(
@@ -849,8 +883,7 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_pv_kernel(
             kv_pair_t<KVT> vv[32];
 #pragma unroll
             for (int j = 0; j < 32; ++j)
-                vv[j] = *reinterpret_cast<const kv_pair_t<KVT>*>(
-                    v_cache + voffs[t + j] + d0);
+                vv[j] = load_v_pair<KVT>(v_cache + voffs[t + j] + d0);
 #pragma unroll
             for (int j = 0; j < 32; ++j) {
                 const float2v vf = kv_pair_f32(vv[j]);
@@ -864,8 +897,7 @@ __global__ __launch_bounds__(DEC_BLOCK) void attn_pv_kernel(
         }
         for (; t < nkeys; ++t) {
             const kv_pair_t<KVT> vv =
-                *reinterpret_cast<const kv_pair_t<KVT>*>(
-                    v_cache + voffs[t] + d0);
+                load_v_pair<KVT>(v_cache + voffs[t] + d0);
             const float2v vf = kv_pair_f32(vv);
             const DEC_LDS float* pt = pw + t * G;
 #pragma unroll
@@ -1102,8 +1134,7 @@ __attribute__((amdgpu_waves_per_eu(4))) void attn_decode_fused_kernel(
             kv_pair_t<KVT> vv[32];
 #pragma unroll
             for (int j = 0; j < 32; ++j)
-                vv[j] = *reinterpret_cast<const kv_pair_t<KVT>*>(
-                    v_cache + voffs[t + j] + d0);
+                vv[j] = load_v_pair<KVT>(v_cache + voffs[t + j] + d0);
 #pragma unroll
             for (int j = 0; j < 32; ++j) {
                 const float2v vf = kv_pair_f32(vv[j]);
@@ -1117,8 +1148,7 @@ __attribute__((amdgpu_waves_per_eu(4))) void attn_decode_fused_kernel(
         }
         for (; t < nkeys; ++t) {
             const kv_pair_t<KVT> vv =
-                *reinterpret_cast<const kv_pair_t<KVT>*>(
-                    v_cache + voffs[t] + d0);
+                load_v_pair<KVT>(v_cache + voffs[t] + d0);
             const float2v vf = kv_pair_f32(vv);
             const DEC_LDS float* pt = pw + t * G;
 #pragma unroll

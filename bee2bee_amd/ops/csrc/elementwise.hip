@@ -157,6 +157,19 @@ __global__ void gelu_kernel(
 // Llama rotate-half RoPE, in place on strided q/k views of the fused qkv
 // projection. One wave per (token, head); lane owns pair (d, d+hd/2).
 // cos/sin tables are host-precomputed fp32 (guide App. B: no device trig).
+//
+// rope_rotate is the one definition of the rotation, for rope_kernel and
+// rope_kv_store_kernel. The two product-and-sums are spelled out as the fma
+// each has always compiled to here, so the bits do not depend on what the
+// optimizer contracts in a given caller:
+//   o1 = fma(x1, c, -(x2 * s)),  o2 = fma(x1, s, x2 * c).
+__device__ __forceinline__ void rope_rotate(float x1, float x2, float c,
+                                            float s, unsigned short& o1,
+                                            unsigned short& o2) {
+    o1 = f2bf(__fmaf_rn(x1, c, -__fmul_rn(x2, s)));
+    o2 = f2bf(__fmaf_rn(x1, s, __fmul_rn(x2, c)));
+}
+
 __global__ void rope_kernel(
     unsigned short* __restrict__ q,  // [T, nq, hd], token stride sq
     unsigned short* __restrict__ k,  // [T, nkv, hd], token stride sk
@@ -179,8 +192,10 @@ __global__ void rope_kernel(
         float s = sin_t[tab + d];
         float x1 = bf2f(base[d]);
         float x2 = bf2f(base[d + half]);
-        base[d] = f2bf(x1 * c - x2 * s);
-        base[d + half] = f2bf(x2 * c + x1 * s);
+        unsigned short o1, o2;
+        rope_rotate(x1, x2, c, s, o1, o2);
+        base[d] = o1;
+        base[d + half] = o2;
     }
 }
 
@@ -356,6 +371,114 @@ __global__ void kv_store_fp8_kernel(
     }
 }
 
+// ------------------------------------------------------------ rope_kv_store
+// rope_kernel followed by kv_store_kernel / kv_store_fp8_kernel in one pass:
+// q and k are rotated in place, and the rotated k and v go to the paged
+// cache. Every q, k and v element is read once, 16 B per lane access.
+//
+// Work item = one lane = 8 dims [8c, 8c + 8) of a head's first half and the
+// matching 8 of its second half, hd / 16 items per head, heads in buffer
+// order q, k, v; items are numbered flat over (token, head, c), so no lane
+// idles but in the last wave. For a q or k head the item is 8 rotation
+// pairs; for a v head it is two 16-byte copies. The lanes of a wave that
+// share c and the token read the same cos / sin addresses, so the tables
+// cost one pair of 32-byte loads per wave instruction, not one per head.
+//
+// The cache receives the converter applied to the bf16-ROUNDED rotated
+// value, the very bits stored in place, so the result is bit for bit the
+// two kernels' (KIND 0: bf16 copy; 1: e4m3; 2: e4m3 of clamp(x * inv[h])).
+// Needs hd % 16 == 0, token strides that are multiples of 8 elements and
+// 16-byte-aligned bases (the binding checks, and runs the two kernels
+// otherwise).
+template <int KIND>
+__device__ __forceinline__ void kv_row_store8(void* cache, long at, short8 x,
+                                              float inv) {
+    if (KIND == 0) {
+        *reinterpret_cast<short8*>((unsigned short*)cache + at) = x;
+        return;
+    }
+    unsigned short w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float a = bf2f((unsigned short)x[2 * i]);
+        float b = bf2f((unsigned short)x[2 * i + 1]);
+        if (KIND == 2) {
+            a = clamp_e4m3(a * inv);
+            b = clamp_e4m3(b * inv);
+        }
+        w[i] = f2fp8x2(a, b);
+    }
+    uint2 o;
+    o.x = (unsigned int)w[0] | ((unsigned int)w[1] << 16);
+    o.y = (unsigned int)w[2] | ((unsigned int)w[3] << 16);
+    *reinterpret_cast<uint2*>((unsigned char*)cache + at) = o;
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(256) rope_kv_store_kernel(
+    unsigned short* q,        // [T, nq, hd], token stride sq
+    unsigned short* k,        // [T, nkv, hd], token stride sk
+    const unsigned short* v,  // [T, nkv, hd], token stride sv
+    void* __restrict__ k_cache,  // [nb, nkv, bs, hd] bf16 or fp8
+    void* __restrict__ v_cache,
+    const int* __restrict__ pos,     // [T]
+    const int* __restrict__ slots,   // [T]
+    const float* __restrict__ cos_t, // [max_len, hd/2]
+    const float* __restrict__ sin_t,
+    const float* __restrict__ k_inv, // [nkv], KIND 2 only
+    const float* __restrict__ v_inv,
+    int T, int nq, int nkv, int hd, int bs, long sq, long sk, long sv) {
+    const int lph = hd / 16;  // lanes per head
+    const int items = (nq + 2 * nkv) * lph;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)T * items) return;
+    const int t = (int)(idx / items);
+    const int r = (int)(idx - (long)t * items);
+    const int h = r / lph;
+    const int d = (r - h * lph) * 8;
+    const int half = hd / 2;
+    BB_KASSERT(t < T && h < nq + 2 * nkv && d + 8 <= half);
+
+    const bool is_q = h < nq;
+    const bool is_v = h >= nq + nkv;
+    const int kvh = is_q ? 0 : (is_v ? h - nq - nkv : h - nq);
+    const unsigned short* src =
+        is_q ? q + (long)t * sq + (long)h * hd
+             : (is_v ? v + (long)t * sv + (long)kvh * hd
+                     : k + (long)t * sk + (long)kvh * hd);
+    short8 x1 = *reinterpret_cast<const short8*>(src + d);
+    short8 x2 = *reinterpret_cast<const short8*>(src + d + half);
+
+    if (!is_v) {
+        const long tab = (long)pos[t] * half + d;
+        const f32x4 c0 = *reinterpret_cast<const f32x4*>(cos_t + tab);
+        const f32x4 c1 = *reinterpret_cast<const f32x4*>(cos_t + tab + 4);
+        const f32x4 s0 = *reinterpret_cast<const f32x4*>(sin_t + tab);
+        const f32x4 s1 = *reinterpret_cast<const f32x4*>(sin_t + tab + 4);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float c = j < 4 ? c0[j & 3] : c1[j & 3];
+            const float s = j < 4 ? s0[j & 3] : s1[j & 3];
+            unsigned short o1, o2;
+            rope_rotate(bf2f((unsigned short)x1[j]),
+                        bf2f((unsigned short)x2[j]), c, s, o1, o2);
+            x1[j] = (short)o1;
+            x2[j] = (short)o2;
+        }
+        unsigned short* dstp = const_cast<unsigned short*>(src);
+        *reinterpret_cast<short8*>(dstp + d) = x1;
+        *reinterpret_cast<short8*>(dstp + d + half) = x2;
+        if (is_q) return;
+    }
+    const int slot = slots[t];
+    const int blk = slot / bs, off = slot % bs;
+    const long dst = (((long)blk * nkv + kvh) * bs + off) * hd;
+    void* cache = is_v ? v_cache : k_cache;
+    const float inv = KIND == 2 ? (is_v ? v_inv[kvh] : k_inv[kvh]) : 1.f;
+    kv_row_store8<KIND>(cache, dst + d, x1, inv);
+    kv_row_store8<KIND>(cache, dst + d + half, x2, inv);
+}
+
 // ----------------------------------------------------------------- swiglu
 // out[t, i] = silu(gu[t, i]) * gu[t, I + i]; grid-stride, short8 loads.
 __global__ void swiglu_kernel(
@@ -470,6 +593,28 @@ void launch_kv_store_fp8(const unsigned short* k, const unsigned short* v,
     hipLaunchKernelGGL(kv_store_fp8_kernel, dim3(blocks), dim3(256), 0,
                        stream, k, v, k_cache, v_cache, slots, k_inv, v_inv, T,
                        nkv, hd, bs, sk, sv);
+}
+
+// kind: 0 = bf16 cache, 1 = fp8 cache at unit scale, 2 = fp8 with per-head
+// reciprocal scales. The caller has checked hd % 16 == 0, the strides and
+// the alignment, and that T * (nq + 2 nkv) * hd / 16 fits an int.
+void launch_rope_kv_store(unsigned short* q, unsigned short* k,
+                          const unsigned short* v, void* k_cache,
+                          void* v_cache, const int* pos, const int* slots,
+                          const float* cos_t, const float* sin_t,
+                          const float* k_inv, const float* v_inv, int kind,
+                          int T, int nq, int nkv, int hd, int bs, long sq,
+                          long sk, long sv, hipStream_t stream) {
+    const long total = (long)T * (nq + 2 * nkv) * (hd / 16);
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+#define BB_ROPE_KV_STORE(KIND)                                                \
+    hipLaunchKernelGGL((rope_kv_store_kernel<KIND>), grid, block, 0, stream,  \
+                       q, k, v, k_cache, v_cache, pos, slots, cos_t, sin_t,   \
+                       k_inv, v_inv, T, nq, nkv, hd, bs, sq, sk, sv)
+    if (kind == 0) BB_ROPE_KV_STORE(0);
+    else if (kind == 1) BB_ROPE_KV_STORE(1);
+    else BB_ROPE_KV_STORE(2);
+#undef BB_ROPE_KV_STORE
 }
 
 void launch_swiglu(const unsigned short* gu, unsigned short* out, long T,

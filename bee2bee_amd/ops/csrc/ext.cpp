@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
+#include <cstdint>
 
 #include "attn_decode.h"
 
@@ -41,6 +42,11 @@ void launch_kv_store_fp8(const unsigned short*, const unsigned short*,
                          unsigned char*, unsigned char*, const int*,
                          const float*, const float*, int, int, int, int, long,
                          long, hipStream_t);
+void launch_rope_kv_store(unsigned short*, unsigned short*,
+                          const unsigned short*, void*, void*, const int*,
+                          const int*, const float*, const float*, const float*,
+                          const float*, int, int, int, int, int, int, long,
+                          long, long, hipStream_t);
 void launch_swiglu(const unsigned short*, unsigned short*, long, long,
                    hipStream_t);
 void launch_attn_prefill(const unsigned short*, const unsigned short*,
@@ -60,11 +66,11 @@ void launch_grouped_gemm(const unsigned short*, const unsigned short*,
                          const int*, unsigned short*, int, int, int, int,
                          hipStream_t);
 void launch_bw_linear(const unsigned short*, long, float*, hipStream_t);
-void launch_bw_rowperlane(const unsigned short*, long, int, int, float*,
+void launch_bw_rowperlane(const unsigned short*, long, int, int, int, float*,
                           hipStream_t);
-void launch_bw_rowperinstr(const unsigned short*, long, int, int, float*,
+void launch_bw_rowperinstr(const unsigned short*, long, int, int, int, float*,
                            hipStream_t);
-void launch_bw_paged(const unsigned short*, const int*, long, int, int,
+void launch_bw_paged(const unsigned short*, const int*, long, int, int, int,
                      float*, hipStream_t);
 void launch_sample_rows(const void*, int, long, int, int, const float*,
                         const int*, const float*, const float*,
@@ -180,8 +186,11 @@ std::vector<Tensor> fused_add_rmsnorm(const Tensor& x, const Tensor& resid,
     return {y, resid_out};
 }
 
-void rope_inplace(Tensor& q, Tensor& k, const Tensor& pos, const Tensor& cos_t,
-                  const Tensor& sin_t) {
+struct RopeDims { int T, nq, nkv, hd; };
+
+// Every check of rope_inplace; rope_kv_store makes the same ones.
+RopeDims check_rope_args(const Tensor& q, const Tensor& k, const Tensor& pos,
+                         const Tensor& cos_t, const Tensor& sin_t) {
     check_bf16(q, "q");
     check_bf16(k, "k");
     TORCH_CHECK(q.dim() == 3 && k.dim() == 3 && k.device() == q.device(),
@@ -210,6 +219,12 @@ void rope_inplace(Tensor& q, Tensor& k, const Tensor& pos, const Tensor& cos_t,
                 "rope: cos and sin must both be [max_len, head_dim / 2] "
                 "contiguous");
     TORCH_CHECK((long)T * (nq + nkv) <= INT_MAX);
+    return {T, nq, nkv, hd};
+}
+
+void rope_inplace(Tensor& q, Tensor& k, const Tensor& pos, const Tensor& cos_t,
+                  const Tensor& sin_t) {
+    const auto [T, nq, nkv, hd] = check_rope_args(q, k, pos, cos_t, sin_t);
     if (T == 0 || nq + nkv == 0) return;
     launch_rope(bf16p_mut(q), bf16p_mut(k), pos.data_ptr<int>(),
                 cos_t.data_ptr<float>(), sin_t.data_ptr<float>(), T, nq, nkv,
@@ -260,10 +275,15 @@ void qk_norm_rope_inplace(Tensor& q, Tensor& k, const Tensor& pos,
     check_launch("qk_norm_rope");
 }
 
-void kv_cache_store(const Tensor& k, const Tensor& v, Tensor& k_cache,
-                    Tensor& v_cache, const Tensor& slots,
-                    const OptTensor& k_inv_scale,
-                    const OptTensor& v_inv_scale) {
+struct StoreDims { int T, nkv, hd, bs; bool scaled; };
+
+// Every check of kv_cache_store that stands before its early return for an
+// empty call; rope_kv_store makes the same ones.
+StoreDims check_kv_store_args(const Tensor& k, const Tensor& v,
+                              const Tensor& k_cache, const Tensor& v_cache,
+                              const Tensor& slots,
+                              const OptTensor& k_inv_scale,
+                              const OptTensor& v_inv_scale) {
     check_bf16(k, "k");
     check_bf16(v, "v");
     TORCH_CHECK(k.dim() == 3 && v.sizes() == k.sizes() &&
@@ -295,27 +315,102 @@ void kv_cache_store(const Tensor& k, const Tensor& v, Tensor& k_cache,
     TORCH_CHECK(k.stride(2) == 1 && k.stride(1) == hd);
     TORCH_CHECK(v.stride(2) == 1 && v.stride(1) == hd);
     TORCH_CHECK(hd % 2 == 0);
-    if (T == 0 || nkv == 0) return;
+    return {T, nkv, hd, bs, scaled};
+}
+
+// The checks of a store that has tokens to write.
+void check_kv_store_target(const Tensor& k_cache) {
     TORCH_CHECK(k_cache.numel() > 0,
                 "kv_cache_store: tokens to store but an empty cache");
+    if (k_cache.scalar_type() != torch::kUInt8) check_bf16(k_cache, "k_cache");
+}
+
+void launch_kv_store_any(const Tensor& k, const Tensor& v, Tensor& k_cache,
+                         Tensor& v_cache, const Tensor& slots,
+                         const OptTensor& k_inv_scale,
+                         const OptTensor& v_inv_scale, const StoreDims& d) {
     if (k_cache.scalar_type() == torch::kUInt8) {
         // fp8 (OCP e4m3) cache: quantize at store time
-        launch_kv_store_fp8(bf16p(k), bf16p(v),
-                            k_cache.data_ptr<unsigned char>(),
-                            v_cache.data_ptr<unsigned char>(),
-                            slots.data_ptr<int>(),
-                            scaled ? k_inv_scale->data_ptr<float>() : nullptr,
-                            scaled ? v_inv_scale->data_ptr<float>() : nullptr,
-                            T, nkv, hd, bs, k.stride(0), v.stride(0),
-                            stream());
-        check_launch("kv_cache_store");
+        launch_kv_store_fp8(
+            bf16p(k), bf16p(v), k_cache.data_ptr<unsigned char>(),
+            v_cache.data_ptr<unsigned char>(), slots.data_ptr<int>(),
+            d.scaled ? k_inv_scale->data_ptr<float>() : nullptr,
+            d.scaled ? v_inv_scale->data_ptr<float>() : nullptr, d.T, d.nkv,
+            d.hd, d.bs, k.stride(0), v.stride(0), stream());
+    } else {
+        launch_kv_store(bf16p(k), bf16p(v), bf16p_mut(k_cache),
+                        bf16p_mut(v_cache), slots.data_ptr<int>(), d.T, d.nkv,
+                        d.hd, d.bs, k.stride(0), v.stride(0), stream());
+    }
+    check_launch("kv_cache_store");
+}
+
+void kv_cache_store(const Tensor& k, const Tensor& v, Tensor& k_cache,
+                    Tensor& v_cache, const Tensor& slots,
+                    const OptTensor& k_inv_scale,
+                    const OptTensor& v_inv_scale) {
+    const StoreDims d = check_kv_store_args(k, v, k_cache, v_cache, slots,
+                                            k_inv_scale, v_inv_scale);
+    if (d.T == 0 || d.nkv == 0) return;
+    check_kv_store_target(k_cache);
+    launch_kv_store_any(k, v, k_cache, v_cache, slots, k_inv_scale,
+                        v_inv_scale, d);
+}
+
+inline bool aligned16(const Tensor& t) {
+    return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+
+// rope_inplace(q, k, ...) followed by kv_cache_store(k, v, ...) as one
+// call: every check of both stands before any launch. One fused kernel
+// where the layout allows 16-byte lane accesses (head_dim % 16 == 0, token
+// strides that are multiples of 8 elements, 16-byte-aligned bases); the two
+// kernels of the separate ops otherwise, with the same result bit for bit.
+void rope_kv_store(Tensor& q, Tensor& k, const Tensor& v, const Tensor& pos,
+                   const Tensor& cos_t, const Tensor& sin_t, Tensor& k_cache,
+                   Tensor& v_cache, const Tensor& slots,
+                   const OptTensor& k_inv_scale,
+                   const OptTensor& v_inv_scale) {
+    const RopeDims r = check_rope_args(q, k, pos, cos_t, sin_t);
+    const StoreDims d = check_kv_store_args(k, v, k_cache, v_cache, slots,
+                                            k_inv_scale, v_inv_scale);
+    TORCH_CHECK(q.device() == k_cache.device() &&
+                    pos.device() == q.device() &&
+                    cos_t.device() == q.device() &&
+                    sin_t.device() == q.device(),
+                "rope_kv_store: every tensor must be on one device");
+    if (r.T == 0) return;
+    if (d.nkv > 0) check_kv_store_target(k_cache);
+    const long items = (long)(r.nq + 2 * r.nkv) * (r.hd / 16);
+    const bool fast =
+        d.nkv > 0 && r.hd % 16 == 0 && q.stride(0) % 8 == 0 &&
+        k.stride(0) % 8 == 0 && v.stride(0) % 8 == 0 && aligned16(q) &&
+        aligned16(k) && aligned16(v) && aligned16(k_cache) &&
+        aligned16(v_cache) && aligned16(cos_t) && aligned16(sin_t) &&
+        (long)r.T * items <= INT_MAX;
+    if (!fast) {
+        if (r.nq + r.nkv > 0) {
+            launch_rope(bf16p_mut(q), bf16p_mut(k), pos.data_ptr<int>(),
+                        cos_t.data_ptr<float>(), sin_t.data_ptr<float>(), r.T,
+                        r.nq, r.nkv, r.hd, q.stride(0), k.stride(0),
+                        stream());
+            check_launch("rope");
+        }
+        if (d.nkv > 0)
+            launch_kv_store_any(k, v, k_cache, v_cache, slots, k_inv_scale,
+                                v_inv_scale, d);
         return;
     }
-    check_bf16(k_cache, "k_cache");
-    launch_kv_store(bf16p(k), bf16p(v), bf16p_mut(k_cache), bf16p_mut(v_cache),
-                    slots.data_ptr<int>(), T, nkv, hd, bs, k.stride(0),
-                    v.stride(0), stream());
-    check_launch("kv_cache_store");
+    const int kind =
+        k_cache.scalar_type() != torch::kUInt8 ? 0 : (d.scaled ? 2 : 1);
+    launch_rope_kv_store(
+        bf16p_mut(q), bf16p_mut(k), bf16p(v), k_cache.data_ptr(),
+        v_cache.data_ptr(), pos.data_ptr<int>(), slots.data_ptr<int>(),
+        cos_t.data_ptr<float>(), sin_t.data_ptr<float>(),
+        d.scaled ? k_inv_scale->data_ptr<float>() : nullptr,
+        d.scaled ? v_inv_scale->data_ptr<float>() : nullptr, kind, r.T, r.nq,
+        r.nkv, r.hd, d.bs, q.stride(0), k.stride(0), v.stride(0), stream());
+    check_launch("rope_kv_store");
 }
 
 Tensor layernorm(const Tensor& x, const Tensor& w, const Tensor& b,
@@ -693,28 +788,52 @@ Tensor mfma_probe(const Tensor& A, const Tensor& B) {
     return C;
 }
 
-void bw_probe_paged(const Tensor& pool, const Tensor& table, int64_t hd,
-                    int64_t rows_per_page) {
+// Pattern probes. mode: 0 linear, 1 row per lane (16 B per lane, the K
+// pattern), 2 row per instruction (4 B per lane, the V pattern); + 4 reads
+// with non-temporal loads (modes 1 and 2). bw_probe_paged: nt != 0 likewise.
+void check_probe_pool(const Tensor& pool, int64_t hd) {
     check_bf16(pool, "pool");
+    TORCH_CHECK(pool.is_contiguous() && hd >= 64 && hd % 64 == 0 &&
+                    pool.numel() >= hd && pool.numel() % hd == 0,
+                "bw_probe: pool must be contiguous, a whole number of rows "
+                "of hd elements, hd a multiple of 64");
+}
+
+void bw_probe_paged(const Tensor& pool, const Tensor& table, int64_t hd,
+                    int64_t rows_per_page, int64_t nt) {
+    check_probe_pool(pool, hd);
+    const long n_rows = pool.numel() / hd;
+    TORCH_CHECK(rows_per_page > 0 && table.is_cuda() &&
+                    table.scalar_type() == torch::kInt32 &&
+                    table.is_contiguous() &&
+                    n_rows % rows_per_page == 0 &&
+                    table.numel() * rows_per_page == n_rows,
+                "bw_probe_paged: the pool must be whole pages and table "
+                "int32 on GPU with one entry (a page index) per page");
     Tensor sink = torch::zeros({1}, pool.options().dtype(torch::kFloat32));
-    launch_bw_paged(bf16p(pool), table.data_ptr<int>(), pool.numel() / hd,
-                    (int)hd, (int)rows_per_page, sink.data_ptr<float>(),
+    launch_bw_paged(bf16p(pool), table.data_ptr<int>(), n_rows, (int)hd,
+                    (int)rows_per_page, (int)nt, sink.data_ptr<float>(),
                     stream());
     check_launch("bw_probe_paged");
 }
 
 void bw_probe(const Tensor& pool, int64_t mode, int64_t hd, int64_t arg) {
-    check_bf16(pool, "pool");
+    check_probe_pool(pool, hd);
+    TORCH_CHECK(mode >= 0 && mode <= 6 && mode != 3 && mode != 4,
+                "bw_probe: mode must be 0, 1, 2, 5 (1 + nt) or 6 (2 + nt)");
     Tensor sink = torch::zeros({1}, pool.options().dtype(torch::kFloat32));
     const long n = pool.numel();
-    if (mode == 0)
+    const int nt = (int)(mode >> 2), pat = (int)(mode & 3);
+    if (pat == 0)
         launch_bw_linear(bf16p(pool), n, sink.data_ptr<float>(), stream());
-    else if (mode == 1)
-        launch_bw_rowperlane(bf16p(pool), n / hd, hd, (int)arg,
+    else if (pat == 1)
+        launch_bw_rowperlane(bf16p(pool), n / hd, hd, (int)arg, nt,
                              sink.data_ptr<float>(), stream());
-    else
-        launch_bw_rowperinstr(bf16p(pool), n / hd, hd, (int)arg,
+    else {
+        TORCH_CHECK(arg > 0, "bw_probe: rows per workgroup must be positive");
+        launch_bw_rowperinstr(bf16p(pool), n / hd, hd, (int)arg, nt,
                               sink.data_ptr<float>(), stream());
+    }
     check_launch("bw_probe");
 }
 
@@ -731,6 +850,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("kv_cache_store", &kv_cache_store, "paged KV scatter",
           py::arg("k"), py::arg("v"), py::arg("k_cache"), py::arg("v_cache"),
           py::arg("slots"), py::arg("k_inv_scale") = py::none(),
+          py::arg("v_inv_scale") = py::none());
+    m.def("rope_kv_store", &rope_kv_store,
+          "rope_inplace then kv_cache_store, one kernel where it can",
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("pos"),
+          py::arg("cos"), py::arg("sin"), py::arg("k_cache"),
+          py::arg("v_cache"), py::arg("slots"),
+          py::arg("k_inv_scale") = py::none(),
           py::arg("v_inv_scale") = py::none());
     m.def("swiglu", &swiglu, "silu(g) * u");
     m.def("layernorm", &layernorm, "LayerNorm (bf16, weight+bias)");
@@ -774,5 +900,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "16x16x32 fp8 MFMA layout probe");
     m.def("grouped_gemm", &grouped_gemm, "per-expert segment GEMM (MoE)");
     m.def("bw_probe", &bw_probe, "bandwidth pattern probe");
-    m.def("bw_probe_paged", &bw_probe_paged, "paged row-per-lane probe");
+    m.def("bw_probe_paged", &bw_probe_paged, "paged row-per-lane probe",
+          py::arg("pool"), py::arg("table"), py::arg("hd"),
+          py::arg("rows_per_page"), py::arg("nt") = 0);
 }

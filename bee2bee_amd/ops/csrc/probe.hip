@@ -60,7 +60,15 @@ extern "C" void launch_mfma_probe_fp8(const unsigned char* A,
 // ---------------------------------------------------------------------------
 // Bandwidth probes over a bf16 pool — used to locate the decode-attention
 // bandwidth ceiling (scripts/bench_attn.py --probe). Each accumulates a
-// checksum so loads cannot be DCE'd.
+// checksum so loads cannot be DCE'd. The three KV-pattern probes (b, c, d)
+// have a non-temporal variant (NT: __builtin_nontemporal_load, the `nt` bit
+// on the global load), which is what DEC_K_NT / DEC_V_NT in attn_decode.hip
+// turn on for the decode kernels' K and V streams.
+template <bool NT, typename T>
+__device__ __forceinline__ T probe_ld(const T* p) {
+    if constexpr (NT) return __builtin_nontemporal_load(p);
+    else return *p;
+}
 
 // (a) linear roofline: grid-stride dwordx4
 __global__ void bw_linear_kernel(const unsigned short* __restrict__ src,
@@ -78,6 +86,7 @@ __global__ void bw_linear_kernel(const unsigned short* __restrict__ src,
 
 // (b) phase-1 pattern: lane owns one 256 B row, reads it in 16 B pieces.
 // rows_per_block keys per workgroup (4 waves x 64), row stride = hd elems.
+template <bool NT>
 __global__ void bw_rowperlane_kernel(const unsigned short* __restrict__ src,
                                      long n_rows, int hd, int batch8,
                                      float* __restrict__ sink) {
@@ -90,7 +99,8 @@ __global__ void bw_rowperlane_kernel(const unsigned short* __restrict__ src,
             short8 raw[8];
 #pragma unroll
             for (int ii = 0; ii < 8; ++ii)
-                raw[ii] = *reinterpret_cast<const short8*>(r + d + ii * 8);
+                raw[ii] = probe_ld<NT>(
+                    reinterpret_cast<const short8*>(r + d + ii * 8));
 #pragma unroll
             for (int ii = 0; ii < 8; ++ii)
 #pragma unroll
@@ -98,7 +108,8 @@ __global__ void bw_rowperlane_kernel(const unsigned short* __restrict__ src,
         }
     } else {
         for (int d = 0; d < hd; d += 8) {
-            short8 v = *reinterpret_cast<const short8*>(r + d);
+            short8 v =
+                probe_ld<NT>(reinterpret_cast<const short8*>(r + d));
 #pragma unroll
             for (int j = 0; j < 8; ++j) acc += (float)(short)v[j];
         }
@@ -108,6 +119,7 @@ __global__ void bw_rowperlane_kernel(const unsigned short* __restrict__ src,
 
 // (c) phase-2 pattern: whole wave reads one row per instruction (4 B/lane),
 // iterating rows in batches of 8 independent loads.
+template <bool NT>
 __global__ void bw_rowperinstr_kernel(const unsigned short* __restrict__ src,
                                       long n_rows, int hd, int rows_per_wg,
                                       float* __restrict__ sink) {
@@ -123,7 +135,8 @@ __global__ void bw_rowperinstr_kernel(const unsigned short* __restrict__ src,
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const long row = (t0 + j < n_rows) ? t0 + j : 0;
-            vv[j] = *reinterpret_cast<const short2v*>(src + row * hd + d0);
+            vv[j] = probe_ld<NT>(
+                reinterpret_cast<const short2v*>(src + row * hd + d0));
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -136,6 +149,7 @@ __global__ void bw_rowperinstr_kernel(const unsigned short* __restrict__ src,
 
 // (d) paged variant of (b): rows resolved through a block table like the
 // KV cache (16 KB pages scattered over the pool)
+template <bool NT>
 __global__ void bw_paged_kernel(const unsigned short* __restrict__ src,
                                 const int* __restrict__ table, long n_rows,
                                 int hd, int rows_per_page,
@@ -150,7 +164,8 @@ __global__ void bw_paged_kernel(const unsigned short* __restrict__ src,
         short8 raw[8];
 #pragma unroll
         for (int ii = 0; ii < 8; ++ii)
-            raw[ii] = *reinterpret_cast<const short8*>(r + d + ii * 8);
+            raw[ii] = probe_ld<NT>(
+                reinterpret_cast<const short8*>(r + d + ii * 8));
 #pragma unroll
         for (int ii = 0; ii < 8; ++ii)
 #pragma unroll
@@ -159,12 +174,18 @@ __global__ void bw_paged_kernel(const unsigned short* __restrict__ src,
     if (acc == 1234.5678f) sink[0] = acc;
 }
 
+// nt != 0 selects the non-temporal variant of a probe.
 extern "C" {
 void launch_bw_paged(const unsigned short* src, const int* table, long n_rows,
-                     int hd, int rows_per_page, float* sink, hipStream_t st) {
+                     int hd, int rows_per_page, int nt, float* sink,
+                     hipStream_t st) {
     long blocks = (n_rows + 255) / 256;
-    hipLaunchKernelGGL(bw_paged_kernel, dim3(blocks), dim3(256), 0, st, src,
-                       table, n_rows, hd, rows_per_page, sink);
+    if (nt)
+        hipLaunchKernelGGL(bw_paged_kernel<true>, dim3(blocks), dim3(256), 0,
+                           st, src, table, n_rows, hd, rows_per_page, sink);
+    else
+        hipLaunchKernelGGL(bw_paged_kernel<false>, dim3(blocks), dim3(256), 0,
+                           st, src, table, n_rows, hd, rows_per_page, sink);
 }
 void launch_bw_linear(const unsigned short* src, long n, float* sink,
                       hipStream_t st) {
@@ -174,15 +195,26 @@ void launch_bw_linear(const unsigned short* src, long n, float* sink,
                        n, sink);
 }
 void launch_bw_rowperlane(const unsigned short* src, long n_rows, int hd,
-                          int batch8, float* sink, hipStream_t st) {
+                          int batch8, int nt, float* sink, hipStream_t st) {
     long blocks = (n_rows + 255) / 256;
-    hipLaunchKernelGGL(bw_rowperlane_kernel, dim3(blocks), dim3(256), 0, st,
-                       src, n_rows, hd, batch8, sink);
+    if (nt)
+        hipLaunchKernelGGL(bw_rowperlane_kernel<true>, dim3(blocks),
+                           dim3(256), 0, st, src, n_rows, hd, batch8, sink);
+    else
+        hipLaunchKernelGGL(bw_rowperlane_kernel<false>, dim3(blocks),
+                           dim3(256), 0, st, src, n_rows, hd, batch8, sink);
 }
 void launch_bw_rowperinstr(const unsigned short* src, long n_rows, int hd,
-                           int rows_per_wg, float* sink, hipStream_t st) {
+                           int rows_per_wg, int nt, float* sink,
+                           hipStream_t st) {
     long blocks = (n_rows + rows_per_wg - 1) / rows_per_wg;
-    hipLaunchKernelGGL(bw_rowperinstr_kernel, dim3(blocks), dim3(256), 0, st,
-                       src, n_rows, hd, rows_per_wg, sink);
+    if (nt)
+        hipLaunchKernelGGL(bw_rowperinstr_kernel<true>, dim3(blocks),
+                           dim3(256), 0, st, src, n_rows, hd, rows_per_wg,
+                           sink);
+    else
+        hipLaunchKernelGGL(bw_rowperinstr_kernel<false>, dim3(blocks),
+                           dim3(256), 0, st, src, n_rows, hd, rows_per_wg,
+                           sink);
 }
 }

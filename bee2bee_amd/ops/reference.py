@@ -207,6 +207,26 @@ def kv_cache_store(
         else _kv_quant_scaled(v, v_inv_scale))
 
 
+def rope_kv_store(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    positions: torch.Tensor,
+    cos: torch.Tensor,
+    sin: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    slot_mapping: torch.Tensor,
+    k_inv_scale: torch.Tensor = None,
+    v_inv_scale: torch.Tensor = None,
+) -> None:
+    """rope_inplace on (q, k), then kv_cache_store of the rotated k and of
+    v: by definition the composition of the two reference ops."""
+    rope_inplace(q, k, positions, cos, sin)
+    kv_cache_store(k, v, k_cache, v_cache, slot_mapping, k_inv_scale,
+                   v_inv_scale)
+
+
 def attn_decode(
     q: torch.Tensor,
     k_cache: torch.Tensor,

@@ -127,37 +127,66 @@ def main():
     _ = out
 
 
-if __name__ == "__main__" and sys.argv[1:2] not in (["probe"], ["paged"]):
+_PROBE_ARGS = (["probe"], ["--probe"], ["paged"], ["--paged"])
+
+if __name__ == "__main__" and sys.argv[1:2] not in _PROBE_ARGS:
     main()
 
 
+def _time_probe(fn, n=10):
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(n):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / n
+
+
 def probe():
-    """Bandwidth probes: python scripts/bench_attn.py probe"""
+    """Bandwidth ceiling of the decode kernels' two read patterns, with
+    plain and with non-temporal (nt) loads side by side, on a 1 GiB pool
+    (four times the Infinity Cache), head_dim 128:
+    python scripts/bench_attn.py --probe
+      row per lane:  a lane reads one key's 256-byte row in 16-byte pieces
+                     (the K pattern), rows in order and through a shuffled
+                     table of 64 KB pages (256 rows, a KV page at bs 256);
+      row per instr: a wave reads one row per instruction, 4 bytes per lane
+                     (the V pattern)."""
     from bee2bee_amd import ops
 
     hip = ops.require_hip()
     dev = "cuda:0"
+    hd = 128
     pool = torch.randn(1 << 29, device=dev).bfloat16()  # 1 GiB
     nbytes = pool.numel() * 2
-    for name, mode, arg in (
-        ("linear dwordx4", 0, 0),
-        ("row-per-lane (serial)", 1, 0),
-        ("row-per-lane (batch8)", 1, 1),
-        ("row-per-instr rpw256", 2, 256),
-        ("row-per-instr rpw1024", 2, 1024),
-    ):
-        for _ in range(2):
-            hip.bw_probe(pool, mode, 128, arg)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(10):
-            hip.bw_probe(pool, mode, 128, arg)
-        torch.cuda.synchronize()
-        dt = (time.perf_counter() - t0) / 10
-        print(f"{name:26s} {nbytes / dt / 1e12:6.2f} TB/s")
+    lin = _time_probe(lambda: hip.bw_probe(pool, 0, hd, 0))
+    print(f"{'linear dwordx4':34s} {nbytes / lin / 1e12:6.2f} TB/s")
+    n_pages = pool.numel() // hd // 256
+    table = torch.randperm(n_pages, device=dev).to(torch.int32)
+    rows = (
+        ("row-per-lane 16 B (serial)", lambda nt: hip.bw_probe(
+            pool, 1 + 4 * nt, hd, 0)),
+        ("row-per-lane 16 B (batch8)", lambda nt: hip.bw_probe(
+            pool, 1 + 4 * nt, hd, 1)),
+        ("row-per-lane 16 B, 64 KB pages", lambda nt: hip.bw_probe_paged(
+            pool, table, hd, 256, nt)),
+        ("row-per-instr 4 B rpw256", lambda nt: hip.bw_probe(
+            pool, 2 + 4 * nt, hd, 256)),
+        ("row-per-instr 4 B rpw1024", lambda nt: hip.bw_probe(
+            pool, 2 + 4 * nt, hd, 1024)),
+    )
+    print(f"{'':34s} {'plain':>11s} {'nt':>11s}")
+    for _round in range(3):  # alternating, three rounds
+        for name, fn in rows:
+            plain = _time_probe(lambda: fn(0))
+            nt = _time_probe(lambda: fn(1))
+            print(f"{name:34s} {nbytes / plain / 1e12:6.2f} TB/s "
+                  f"{nbytes / nt / 1e12:6.2f} TB/s")
 
 
-if __name__ == "__main__" and "probe" in sys.argv[1:2]:
+if __name__ == "__main__" and sys.argv[1:2] in (["probe"], ["--probe"]):
     probe()
     sys.exit(0)
 
@@ -177,19 +206,15 @@ def probe_paged():
                 torch.randperm(n_pages, device=dev)
                 if perm else torch.arange(n_pages, device=dev)
             ).to(torch.int32)
-            for _ in range(2):
-                hip.bw_probe_paged(pool, table, hd, rpp)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(10):
-                hip.bw_probe_paged(pool, table, hd, rpp)
-            torch.cuda.synchronize()
-            dt = (time.perf_counter() - t0) / 10
+            dts = [_time_probe(
+                lambda: hip.bw_probe_paged(pool, table, hd, rpp, nt))
+                for nt in (0, 1)]
             print(f"paged rows/page={rpp:4d} {name:5s}"
                   f" ({rpp * hd * 2 // 1024:3d} KB contig) "
-                  f"{nbytes / dt / 1e12:6.2f} TB/s")
+                  f"{nbytes / dts[0] / 1e12:6.2f} TB/s plain "
+                  f"{nbytes / dts[1] / 1e12:6.2f} TB/s nt")
 
 
-if __name__ == "__main__" and "paged" in sys.argv[1:2]:
+if __name__ == "__main__" and sys.argv[1:2] in (["paged"], ["--paged"]):
     probe_paged()
     sys.exit(0)

@@ -2,7 +2,14 @@
 r1 rocprofv3 emitted (Name,Calls,TotalDurationNs,AverageNs,Percentage,
 MinNs,MaxNs,StdDev) so `profiles/` stays one consistent format.
 
-Usage: python scripts/rocpd_stats.py <results.db> <out.csv>
+Usage: python scripts/rocpd_stats.py <results.db> <out.csv> [--decode-only]
+
+--decode-only keeps the decode dispatches of a bench.py trace: everything
+from the first RoPE dispatch (a kernel whose name holds "rope") that starts
+after the last prefill-attention dispatch (a name holding "attn_prefill")
+has ended. The prefill's own tail (its last layers' GEMMs and norms, the
+lm_head) lies before that dispatch; what the cut loses of the decode is the
+first decode step's first rmsnorm and qkv GEMM, one call each.
 """
 import csv
 import math
@@ -12,6 +19,7 @@ import sys
 
 def main() -> None:
     db_path, out_path = sys.argv[1], sys.argv[2]
+    decode_only = "--decode-only" in sys.argv[3:]
     db = sqlite3.connect(db_path)
     cur = db.cursor()
     tables = [r[0] for r in cur.execute(
@@ -19,8 +27,19 @@ def main() -> None:
     kd = next(t for t in tables if t.startswith("rocpd_kernel_dispatch"))
     ks = next(t for t in tables if t.startswith("rocpd_info_kernel_symbol"))
     rows = list(cur.execute(
-        f"SELECT s.display_name, d.end - d.start FROM {kd} d "
+        f"SELECT s.display_name, d.end - d.start, d.start, d.end FROM {kd} d "
         f"JOIN {ks} s ON s.id = d.kernel_id"))
+    if decode_only:
+        prefill_end = max((e for n, _, _, e in rows if "attn_prefill" in n),
+                          default=None)
+        if prefill_end is None:
+            raise SystemExit("--decode-only: no attn_prefill dispatch")
+        t0 = min((s for n, _, s, _ in rows
+                  if "rope" in n and s >= prefill_end), default=None)
+        if t0 is None:
+            raise SystemExit("--decode-only: no rope dispatch after prefill")
+        rows = [r for r in rows if r[2] >= t0]
+    rows = [(n, d) for n, d, _, _ in rows]
     agg = {}
     for name, dur in rows:
         agg.setdefault(name, []).append(dur)
